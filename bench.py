@@ -7,11 +7,16 @@ heads forward, on-device matching + loss, backward, RMSProp/EMA) on 299x299 synt
   python bench.py --gpus N ...          (starts N ranks itself: launch_plan / spawn_ranks below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (the MFMA implicit-GEMM
-convolution, forward + data-gradient launches) from the kernels' begin/end timestamps over three extra
-real steps after the timed region (ROCm tracer via torch.profiler; HIP-event intervals of one eager
-pass as a cross-check); `cpu_baseline` times the restated CPU reference
-(oracle/cpu_train.py) on a bounded sample on the host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the
+line (`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what one step of the timed path
+computes from the seeded starting state (dump_outputs below).  Everything else it measures runs only
+under `--full`: `roofline` prices the dominant kernel (the MFMA implicit-GEMM convolution, forward +
+data-gradient launches) from the kernels' begin/end timestamps over three extra real steps after the
+timed region (ROCm tracer via torch.profiler; HIP-event intervals of one eager pass as a cross-check); `cpu_baseline` times the restated CPU reference
+(oracle/cpu_train.py) on a bounded sample on the host cores; `detect`, `input_augment` and `configs`
+are the other BASELINE configurations.  The --no-* switches leave parts of a --full run out.
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -26,10 +31,10 @@ MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: ~2.5 PF dense bf
 HBM_PEAK_GBS = 8000.0
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="BATCH_SIZE per GPU (BASELINE configs[1]: 64)")
     ap.add_argument("--input-size", type=int, default=299)
@@ -46,7 +51,81 @@ def parse():
     ap.add_argument("--log-losses", action="store_true", help="print the loss after every step to stderr (adds host syncs)")
     ap.add_argument("--no-configs", action="store_true", help="skip the other single-GPU BASELINE configurations (fine-tune, 512x512)")
     ap.add_argument("--config-steps", type=int, default=10)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / kernel trace, CPU baseline, detect and input-augmentation legs and the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one step of the timed path computes from the seeded starting state as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_MAX_ELEMENTS = 1 << 20      # per array (4 MB of float32): the arrays of dump_outputs stay far below 64 MB
+
+
+def dump_indices(n, seed=0):
+    """Positions of the fixed, seeded sample dump_outputs keeps of a flat array of n elements (None: all of them)."""
+    import numpy as np
+    if n <= DUMP_MAX_ELEMENTS:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, DUMP_MAX_ELEMENTS))
+
+
+def training_state(tr, net):
+    """Every buffer a training step reads and the optimiser rewrites (parameters, their bf16 copy, RMSProp / momentum
+    slots, EMA shadows, batch-norm moving statistics); the rest of a step is recomputed from these and the batch."""
+    ts = [net.W, net.Wb, net.Bt, net.MM, net.MV, tr.Wms, tr.Btms, tr.Wmom, tr.Btmom, tr.Wema, tr.Btema, tr.MMema, tr.MVema]
+    return [t for t in ts if t is not None]
+
+
+def dump_outputs(path, tr, net, seeded_state, rank=0, pg=None):
+    """--dump-outputs: one step of the timed path (Trainer.step, the same captured graphs) from the seeded state the timed
+    steps started from, and what it computed, as DIR/<name>.npy: the losses (float64: location, confidence,
+    regularization, total), the heads' predictions of its forward pass, the loss gradients it took of them, the
+    batch-norm moving statistics it left, and, for the Multibox heads, the weight / beta gradients of its backward pass
+    and the parameters the RMSProp update left (float32).  seeded_state = (global_step, copies of training_state())
+    from before the warm-up.
+    Why one step from the seeded state, and why the heads: outside MBX_DETERMINISTIC mode the one-launch batch-norm
+    backward sums its per-channel statistics with float atomics, and the activation gradient it returns is the small
+    difference of large terms, so below the first such layer the gradients of one step from the same state differ
+    between runs by up to ~10 % (relative L2 per tensor; 2e-7 with the three-launch form), and so do the weights updated
+    from them and every later step.  The heads' gradients come from the loss before any such layer: they agree between
+    runs to the rounding of their float-atomic sums (measured 2.4e-5 of the largest gradient; 7e-4 of the largest head
+    weight after the update).  An array of more than DUMP_MAX_ELEMENTS elements is stored flat as the seeded sample dump_indices()
+    picks, so that two builds can be compared output for output.  Every rank takes the step (a data-parallel step
+    all-reduces); rank 0 writes."""
+    import numpy as np
+    import torch
+    step0, saved = seeded_state
+    for t, s in zip(training_state(tr, net), saved):
+        t.copy_(s)
+    net.prepare_filters()                          # (the data-gradient filter copies follow the bf16 filters)
+    tr.global_step = step0
+    skipped = int(tr.skipped_steps)
+    tr.step()
+    # the verdict over ALL ranks (every rank raises or none: a rank left behind would wait in the next collective)
+    bad = torch.tensor([int(tr.skipped_steps) - skipped, int(tr.match_status().max() != 0)], dtype=torch.int32, device=net.W.device)
+    if pg is not None:
+        torch.distributed.all_reduce(bad, group=pg)
+    if int(bad.sum()) != 0:
+        raise RuntimeError("--dump-outputs: the step from the seeded state was not applied on every rank "
+                           "(skipped on %d, matching failed on %d)" % tuple(bad.tolist()))
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    hw, hb = net.head_w_start, net.head_bt_start
+    arrays = {"locs": net.locs, "logits": net.logits, "loc_gradients": net.d_locs, "logit_gradients": net.d_logits,
+              "moving_mean": net.MM, "moving_variance": net.MV,
+              "head_weight_gradients": net.Wg[hw:], "head_weights": net.W[hw:], "head_weights_ema": tr.Wema[hw:],
+              "head_beta_gradients": net.Btg[hb:net.nBt], "head_beta": net.Bt[hb:]}
+    for name, t in arrays.items():
+        t = t.detach()
+        idx = dump_indices(t.numel())
+        if idx is not None:
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+    np.save(os.path.join(path, "losses.npy"), np.array(tr.losses(), np.float64))
 
 
 def launch_plan(gpus, env, argv, visible_devices, script=None, port=None):
@@ -652,6 +731,7 @@ def main():
                  decay_steps_=decay_steps(56945, B * world, 4), use_graph=not args.no_graph, process_group=pg)
     images, gt, n = synthetic_batch(B, args.input_size, args.max_num_bboxes, seed=100 * rank)    # each rank its own shard
     tr.set_batch(torch.from_numpy(images).cuda(), torch.from_numpy(gt).cuda(), torch.from_numpy(n).cuda())
+    seeded_state = (tr.global_step, [t.clone() for t in training_state(tr, net)]) if args.dump_outputs else None
 
     def sync():
         if pg is not None:
@@ -674,6 +754,7 @@ def main():
     dt_own = time.perf_counter() - t0          # this rank alone (before the closing barrier)
     sync()
     dt = time.perf_counter() - t0
+    roofline = args.full and not args.no_roofline
     dp_diag = None
     if pg is not None:
         exposed = [a.elapsed_time(b) for a, b in tr.exposed_events]
@@ -743,15 +824,18 @@ def main():
             out["data_parallel"] = dp_diag
         from multibox_amd import ops as _ops
         out["tune_cache"] = dict(_ops.TUNE_STATS)      # table entries accepted as they are / shapes measured on THIS box / refused
+    if args.dump_outputs:                      # (after the line's losses and health are read: it takes one more step)
+        dump_outputs(args.dump_outputs, tr, net, seeded_state, rank, pg)
+        del seeded_state
     traced = None
     eager = None
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
         try:
             eager = timed_eager_pass(tr.run_eager_once)       # (work and launch counts per kernel class; also what a complete trace must show)
             EXPECT_IGEMM_LAUNCHES[0] = eager[0]["igemm"]["calls"]
         except Exception as e:
             eager = e
-    if not args.no_roofline:                # three more real steps on EVERY rank (the all-reduce needs them all); rank 0 traces its kernels
+    if roofline:                            # three more real steps on EVERY rank (the all-reduce needs them all); rank 0 traces its kernels
         if rank == 0:
             done = [0]
 
@@ -773,7 +857,7 @@ def main():
             for _ in range(3):
                 tr.step()
             torch.cuda.synchronize()
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
         try:
             if isinstance(eager, Exception):
                 raise eager
@@ -789,14 +873,14 @@ def main():
     if pg is not None:
         torch.distributed.barrier()
     cpu_base = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         try:
             cpu_base = cpu_baseline(net, priors, args.cpu_seconds)
         except Exception as e:
             cpu_base = {"error": repr(e)}
     del tr, net                     # free the training buffers before the other networks are built
     torch.cuda.empty_cache()
-    if not args.no_detect:
+    if args.full and not args.no_detect:
         try:
             dleg = detect_leg(args, world, rank, pg)
         except Exception as e:
@@ -809,7 +893,7 @@ def main():
                 out["input_augment"] = {"error": repr(e)}
         if pg is not None:
             torch.distributed.barrier()
-    if rank == 0 and world == 1 and not args.no_configs and not args.fine_tune and (args.input_size, args.k) == (299, 5):
+    if rank == 0 and world == 1 and args.full and not args.no_configs and not args.fine_tune and (args.input_size, args.k) == (299, 5):
         cfgs = {}
         for key, ft, S_, k_, G_, label in (
                 ("fine_tune", True, 299, 5, 13, "train.py --fine_tune (frozen backbone, heads train: BASELINE config 1's semantics), "

@@ -258,7 +258,7 @@ def test_bench_contract_over_rccl(tmp_path):
     env = dict(os.environ, PYTHONPATH=ROOT, MBX_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+                        "--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -270,6 +270,47 @@ def test_bench_contract_over_rccl(tmp_path):
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["scaling"] == "weak" and out["vs_baseline"] is None
     assert out["matching_ok"] and out["grid_barrier_timeouts"] == 0 and out["value"] > 0
     assert out["roofline"]["bound"] == "mfma" and 0 < out["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone, and --dump-outputs writes what one step of the
+    timed path computes from the seeded starting state.  A run of 2 + 3 steps and a run whose one timed step IS that first
+    step write the same arrays: the inputs are the same in every run and the dump's step starts from the seeded state,
+    not from wherever the timed steps left the weights.  Bit-identical except the losses and the heads' gradients and
+    updated parameters, which are float-atomic sums (to rounding, stated below)."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    dumps = []
+    for i, (steps, warmup) in enumerate(((3, 2), (1, 0))):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["warmup"] == warmup and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert out["matching_ok"] and out["grid_barrier_timeouts"] == 0
+        assert not {"roofline", "cpu_baseline", "detect", "input_augment", "configs"} & set(out), sorted(out)
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f[:-len(".npy")]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["losses"].shape == (4,) and np.isfinite(arrays["losses"]).all()
+        assert arrays["locs"].shape[0] == 64 and arrays["locs"].shape[2] == 4 and arrays["logits"].shape == arrays["locs"].shape[:2]
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    np.testing.assert_allclose(dumps[0].pop("losses"), dumps[1].pop("losses"), rtol=1e-5)
+    for name in dumps[0]:
+        a, b = dumps[0][name], dumps[1][name]
+        if name.startswith("head_") and name != "head_weights_ema":
+            # the heads' backward and update: the weight gradient is a float-atomic sum.  Measured between runs: gradients
+            # 2.4e-5 of the array's largest value, updated parameters 7.2e-4 (the update carries the gradient's difference)
+            tol = 1e-4 if name.endswith("_gradients") else 3e-3
+            assert np.abs(a - b).max() <= tol * np.abs(a).max(), (name, np.abs(a - b).max(), np.abs(a).max())
+        else:
+            assert np.array_equal(a, b), name
 
 
 def test_bench_gpus_2_on_a_one_gpu_box_refuses():

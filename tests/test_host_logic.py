@@ -308,6 +308,23 @@ def test_bench_gpus_flag_starts_that_many_ranks_or_refuses():
         assert r.returncode == 2 and "--gpus 2" in r.stderr and "{" not in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-500:])
 
 
+def test_bench_plain_run_options_and_dump_sample():
+    """bench.py: --full is off by default (a plain run times the headline alone), --steps sets the timed steps, and the
+    sample --dump-outputs keeps of a large array is the same sorted positions in every run."""
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "1"])
+    assert a.steps == 7 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    assert bench.dump_indices(bench.DUMP_MAX_ELEMENTS) is None
+    n = 55 * 10 ** 6
+    i = bench.dump_indices(n)
+    assert np.array_equal(i, bench.dump_indices(n)) and bench.DUMP_MAX_ELEMENTS // 2 < len(i) <= bench.DUMP_MAX_ELEMENTS
+    assert (np.diff(i) > 0).all() and 0 <= i[0] and i[-1] < n
+
+
 def test_grid_barrier_cap_is_derived_from_rccl_channels():
     """the workgroup cap of the grid-barrier launches in a data-parallel run = CUs - RCCL's channels."""
     from multibox_amd.dist import bn_max_workgroups_for, rccl_cu_reserve

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence of a round on the GPU box (run through gpurun; outputs under gpurun_out/prof_$1).
-#   part a: the default bench line, kernel stats + per-layer table of the traced bench, FETCH_SIZE / WRITE_SIZE passes
+#   part a: the full bench line (--full), kernel stats + per-layer table of the traced bench, FETCH_SIZE / WRITE_SIZE passes
 #           (separate --pmc runs, eager steps; tools/pmc_traffic.py applies the gfx950 FETCH_SIZE x2 correction)
 #   part b: SQ counters of every convolution kernel instantiation of the step (two --pmc passes), the grouped weight gradient
 #   part c: the 2000-step saturation stress, the 512x512 configuration
@@ -14,7 +14,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 B="--steps 2 --warmup 1 --no-graph --no-roofline --no-cpu-baseline --no-detect --no-configs"
 if [ "$part" = "a" ]; then
-  python bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
+  python bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o kt -- python3 bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-detect --no-roofline --no-configs > $out/bench_prof.json 2> $out/bench_prof.err || exit 2
   python tools/trace_by_layer.py $out/kt/kt_kernel_trace.csv > $out/by_layer.txt 2>&1
   cp $out/kt/kt_kernel_stats.csv $out/kernel_stats.csv
@@ -53,6 +53,6 @@ elif [ "$part" = "d" ]; then
   rm -rf $out/df $out/dw
 elif [ "$part" = "c" ]; then
   MBX_DETERMINISTIC=1 python tools/side_stream_stress.py 2000 compare saturate > $out/saturation_stress.json 2> >(tee $out/saturation_stress.err >&2) || exit 7
-  python bench.py --input-size 512 --k 7 --max-num-bboxes 100 --no-cpu-baseline --no-detect --no-configs > $out/bench_512.json 2> $out/bench_512.err
+  python bench.py --full --input-size 512 --k 7 --max-num-bboxes 100 --no-cpu-baseline --no-detect --no-configs > $out/bench_512.json 2> $out/bench_512.err
 fi
 ls -la $out

@@ -24,9 +24,14 @@ def parse_args():
     p.add_argument("--config", dest="config_file", type=str, required=True)
     p.add_argument("--max_iterations", dest="max_iterations", type=int, default=0)
     p.add_argument("--max_detections", dest="max_detections", type=int, default=100,
-                   help="accepted for compatibility; unused by the reference too (detect.py:294)")
+                   help="with --merge_per_image: the most detections kept per image in results-merged-<step>.json; otherwise "
+                        "accepted for compatibility and unused, as in the reference (detect.py:294)")
     p.add_argument("--save_dir", dest="save_dir", type=str, required=True)
     p.add_argument("--synthetic", type=int, default=0, help="[new] number of synthetic images instead of --tfrecords")
+    p.add_argument("--merge_per_image", action="store_true",
+                   help="[new] also write results-merged-<global_step>.json: per image, the candidates of all its patches "
+                        "ordered by score, de-duplicated by greedy NMS across patches (DETECTION.MERGE_IOU_THRESHOLD, "
+                        "default 0.5; null = none) and cut to --max_detections")
     p.add_argument("--keep_partial_batch", action="store_true",
                    help="[new] also process the last incomplete batch (the reference's tf.train.batch drops it)")
     return p.parse_args()
@@ -157,10 +162,32 @@ def main():
         pool = ProcessPoolExecutor(max_workers=n_workers, mp_context=mp.get_context("spawn"))
     from multibox_amd import records as REC
 
+    # --merge_per_image (not in the reference): one ImageMerger on rank 0, fed with the host copies of every batch in batch
+    # order.  One rank feeds it as the batches finish; with several, an image's patches are spread over the ranks, so every
+    # rank keeps its rows compacted and rank 0 feeds them after the gather.  The merge launches are eager, outside the graph.
+    merger, merge_rows, tail = None, [], [None, 0, None]
+    if args.merge_per_image:
+        # DETECTION.MERGE_IOU_THRESHOLD (not a key of the reference): 0.5 when absent, null = no suppression (top-N per image)
+        merge_iou = det.get("MERGE_IOU_THRESHOLD", 0.5)
+        if rank == 0:
+            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou)
+
+    def merge_feed(hb, hs, hc, ids_, hw_last):
+        merger.add(hb, hs, hc, ids_)
+        n = 0
+        while n < len(ids_) and ids_[-1 - n] == ids_[-1]:
+            n += 1
+        tail[:] = [ids_[-1], n + (tail[1] if n == len(ids_) and tail[0] == ids_[-1] else 0), hw_last]
+
     def finish(p):
-        slot, bi_, ids_ = p
+        slot, bi_, ids_, hw_last = p
         ev[slot][2].synchronize()
         hb, hs, hc = host_out[slot]
+        if args.merge_per_image:
+            if world == 1:
+                merge_feed(hb.numpy(), hs.numpy(), hc.numpy(), ids_, hw_last)
+            else:
+                merge_rows.append((bi_, [REC.compact_rows(hb.numpy(), hs.numpy(), hc.numpy()) + (ids_, hw_last)]))
         if pool is not None:
             results.append((bi_, pool.submit(REC.batch_chunk, hb.numpy().copy(), hs.numpy().copy(), hc.numpy().copy(), ids_)))
         else:
@@ -191,7 +218,7 @@ def main():
         ids = [int(i) if str(i).lstrip("-").isdigit() else i for i in batch["image_ids"]]     # detect.py:410 int(image_id)
         if pending is not None:
             finish(pending)
-        pending = (slot, bi, ids)
+        pending = (slot, bi, ids, tuple(int(v) for v in batch["image_hw"][-1]))
         step += 1
         if args.max_iterations > 0 and step == args.max_iterations:
             break
@@ -219,6 +246,23 @@ def main():
         with open(save_path, "w") as f:
             f.write(D.records_to_json(results))        # the same text as json.dump(list of record dicts, f)
         print("wrote", save_path, n_records, "detections")
+    if args.merge_per_image:
+        if world > 1:
+            parts = D.gather_results(merge_rows)       # rank 0: every batch's compacted rows, in batch order
+            for cnt_, bv, sv, ids_, hw_last in (parts if rank == 0 else []):
+                merge_feed(*REC.expand_rows(cnt_, bv, sv, max_keep), ids_, hw_last)
+        if rank == 0:
+            if args.tfrecords and not args.synthetic and not args.keep_partial_batch and tail[0] is not None:
+                from multibox_amd.inputs import detect_patch_plan
+                want = len(detect_patch_plan(tail[2][0], tail[2][1], tail[2], cfg))
+                if tail[1] < want:      # the reference drops the last incomplete batch (tf.train.batch); so does this
+                    print("image %s: merged from %d of its %d patches (the rest fell into the dropped incomplete last batch; "
+                          "--keep_partial_batch processes it)" % (tail[0], tail[1], want))
+            m_ids, m_boxes, m_scores, m_count = merger.finish()
+            save_path = os.path.join(args.save_dir, "results-merged-%d.json" % global_step)
+            with open(save_path, "w") as f:
+                f.write(D.records_to_json(REC.results_to_json_text(m_boxes, m_scores, m_count, m_ids)))
+            print("wrote", save_path, int(m_count.sum()), "detections of", len(m_ids), "images")
     if world > 1:
         torch.distributed.destroy_process_group()
 

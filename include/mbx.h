@@ -121,6 +121,25 @@ int mbx_decode_filter_topk(const float* raw_locs /*[B,P,4]*/, const float* conf 
 int mbx_nms(double* boxes /*[B,k_max,4] x1,y1,x2,y2*/, float* scores /*[B,k_max]*/, int32_t* index /*[B,k_max]*/,
             int32_t* count /*[B], in/out*/, int B, int k_max, double iou_threshold, mbx_stream_t stream);
 
+/* OPTIONAL per-image merge of multi-crop detections (not in the reference, which writes every patch's boxes one after the
+ * other -- detect.py:438-460 -- so an object is reported once per patch that sees it).  Input: exactly what
+ * mbx_decode_filter_topk (+ mbx_nms) writes, rows in stream order; image i owns rows [image_rows[i], image_rows[i+1]).
+ * Per image: the candidates are the slots [0, count[r]) of its rows (count clamped to [0, k_max]; a row need not be
+ * sorted), flat index row * k_max + slot.  They are ordered by score descending, ties by ascending flat index (the same
+ * order-preserving image of the float bits as mbx_decode_filter_topk: -0 == +0, a NaN first), and walked greedily: a
+ * candidate is kept iff its IoU with every earlier KEPT candidate is <= iou_threshold (float64, the operation order of
+ * mbx_nms; +infinity = no suppression, no IoU is evaluated), until max_det are kept or the list ends.  Kept candidates go
+ * out in kept order: out_boxes (the source's bytes), out_scores, out_src (flat index), out_count[i]; unused slots are
+ * 0 / 0 / -1.  out_status[i]: 0 ok; 1 = more than MBX_MERGE_MAX_CANDIDATES candidates, out_count[i] = 0 (the caller cuts
+ * such an image down first).  I == 0: MBX_OK, nothing launched.  max_det <= 640 (what the kernel's LDS holds beside the
+ * 16 384 sort keys), above: MBX_ERR_UNSUPPORTED.  Not in place, one workgroup per image.                            */
+#define MBX_MERGE_MAX_CANDIDATES 16384
+int mbx_merge_detections(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const float* scores /*[R,k_max]*/,
+                         const int32_t* count /*[R]*/, const int32_t* image_rows /*[I+1] ascending*/, int I, int k_max,
+                         int max_det, double iou_threshold, double* out_boxes /*[I,max_det,4]*/,
+                         float* out_scores /*[I,max_det]*/, int32_t* out_src /*[I,max_det]*/,
+                         int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ convolution stack (A2-A4)
  * Replaces slim.conv2d (+ batch_norm + relu) of model.py:6-324 and its TF gradients
  * (train.py:263).  Activations are NHWC bf16 *views*: element (n,h,w,c) of a tensor lives at

@@ -39,6 +39,7 @@ _SIGS = {
     "mbx_loss_fwd_bwd": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, P, SZ, P]),
     "mbx_decode_filter_topk": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "mbx_nms": (I, [P, P, P, P, I, I, C.c_double, P]),
+    "mbx_merge_detections": (I, [P, P, P, P, I, I, I, C.c_double, P, P, P, P, P, P]),
     "mbx_augment_workspace_bytes": (SZ, [I, I]),
     "mbx_augment_batch": (I, [P, P, I, I, I, P, P, P]),
     "mbx_extract_patches": (I, [P, P, I, I, P, P]),

@@ -1,0 +1,216 @@
+// libmbx: per-image merge of multi-crop detections (greedy NMS across patches + top-N).
+// The reference writes every patch's boxes one after the other (detect.py:408-460) and has no such stage; this one is
+// optional and sits behind mbx_decode_filter_topk (+ mbx_nms), reading exactly what they write.  Built with
+// -ffp-contract=off: the float64 IoU keeps the operation order of oracle.ref_numpy.nms_greedy, so keep decisions are exact.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxCand = MBX_MERGE_MAX_CANDIDATES;
+// LDS plan of merge_kernel: keys [16384] u64, kept boxes [max_det][4] f64, kept offsets [max_det] i32, the boxes of one
+// chunk of kThreads candidates [kThreads][4] f64.  640 is what fits beside the keys in the 160 KiB of a workgroup.
+constexpr int kMergeMaxDet = 640;
+
+struct Box { double x1, y1, x2, y2; };
+
+// does the EARLIER (kept) box e suppress the later box b of area ab?  oracle.ref_numpy.nms_greedy, term by term
+__device__ __forceinline__ bool suppresses(const Box& e, const Box& b, double ab, double thr) {
+  const double iw = fmin(e.x2, b.x2) - fmax(e.x1, b.x1), ih = fmin(e.y2, b.y2) - fmax(e.y1, b.y1);
+  const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
+  const double uni = (e.x2 - e.x1) * (e.y2 - e.y1) + ab - inter;
+  const double iou = uni > 0.0 ? inter / uni : 0.0;
+  return iou > thr;
+}
+
+__device__ __forceinline__ Box box_shfl(const Box& b, int src) {
+  Box r;
+  r.x1 = __shfl(b.x1, src, 64); r.y1 = __shfl(b.y1, src, 64);
+  r.x2 = __shfl(b.x2, src, 64); r.y2 = __shfl(b.y2, src, 64);
+  return r;
+}
+
+// One workgroup per image.
+//   1. candidates = slots [0, count[r]) of the image's rows; key = order-preserving image of the score's float bits
+//      (as decode_filter_topk_kernel: -0 == +0, NaN above everything) << 32 | ~(offset of the slot from the image's first
+//      slot): a descending sort gives score descending, ties by ascending flat index.  Bitonic sort in LDS.
+//   2. walk the sorted list kThreads candidates at a time: every thread tests its candidate against the kept list as it
+//      stands (kept boxes in LDS, broadcast reads); then wave 0 goes through the chunk 64 at a time, tests the survivors
+//      against what the chunk itself has added since, resolves the 64 among themselves in order (ballot + shuffle of
+//      the next kept box) and appends.  Stops at max_det kept.
+//   3. kept boxes / scores / flat indices go out in kept order, unused slots 0 / 0 / -1.
+__global__ void __launch_bounds__(kThreads)
+merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ count,
+             const int32_t* __restrict__ image_rows, int k_max, int max_det, double thr, int use_iou,
+             double* __restrict__ out_boxes, float* __restrict__ out_scores, int32_t* __restrict__ out_src,
+             int32_t* __restrict__ out_count, int32_t* __restrict__ out_status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char merge_lds[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(merge_lds);       // [kMaxCand]
+  Box* kept = reinterpret_cast<Box*>(keys + kMaxCand);                                // [max_det]
+  Box* chunk = kept + max_det;                                                        // [kThreads]
+  unsigned* kept_rel = reinterpret_cast<unsigned*>(chunk + kThreads);                 // [max_det]
+  __shared__ int tile_cnt[kThreads];
+  __shared__ int wave_tot[kWaves];
+  __shared__ unsigned long long alive_mask[kWaves];
+  __shared__ int sh_nk;
+
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int r0 = image_rows[img], r1 = image_rows[img + 1];
+  const long long base = (long long)r0 * k_max;                 // flat index of the image's first slot
+  double* ob = out_boxes + (size_t)img * max_det * 4;
+  float* os = out_scores + (size_t)img * max_det;
+  int32_t* oi = out_src + (size_t)img * max_det;
+
+  // ---- 1a. number of candidates
+  int mine = 0;
+  for (int r = r0 + tid; r < r1; r += kThreads) mine += min(max(count[r], 0), k_max);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  if (lane == 0) wave_tot[tid >> 6] = mine;
+  if (tid == 0) sh_nk = 0;
+  __syncthreads();
+  int total = 0;
+  for (int w = 0; w < kWaves; ++w) total += wave_tot[w];
+  const bool too_many = total > kMaxCand;
+  if (too_many) total = 0;
+
+  int nk = 0;
+  if (total > 0) {
+    // ---- 1b. keys
+    int N = 64;
+    while (N < total) N <<= 1;
+    int off = 0;
+    for (int t0 = r0; t0 < r1; t0 += kThreads) {
+      const int nrows = min(kThreads, r1 - t0);
+      __syncthreads();                                           // the previous tile's counts have been read
+      if (tid < nrows) tile_cnt[tid] = min(max(count[t0 + tid], 0), k_max);
+      __syncthreads();
+      for (int q = 0; q < nrows; ++q) {
+        const int c = tile_cnt[q];
+        const float* sr = scores + (size_t)(t0 + q) * k_max;
+        const unsigned rel0 = (unsigned)(t0 + q - r0) * (unsigned)k_max;
+        for (int s = tid; s < c; s += kThreads) {
+          const float v = sr[s];
+          unsigned u = __float_as_uint(v);
+          u = (v != v) ? 0xffffffffu : (v == 0.f) ? 0x80000000u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));   // -0 == +0
+          keys[off + s] = ((unsigned long long)u << 32) | (unsigned long long)(~(rel0 + (unsigned)s));
+        }
+        off += c;
+      }
+    }
+    for (int j = total + tid; j < N; j += kThreads) keys[j] = 0ull;      // below every candidate's key (its score image is > 0)
+    __syncthreads();
+    for (int size = 2; size <= N; size <<= 1) {
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = tid; t < (N >> 1); t += kThreads) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool desc = (lo & size) == 0;
+          const unsigned long long a = keys[lo], bb = keys[hi];
+          if ((a < bb) == desc) { keys[lo] = bb; keys[hi] = a; }
+        }
+        __syncthreads();
+      }
+    }
+
+    if (!use_iou) {
+      // ---- 2'. no suppression: the first max_det of the sorted list
+      nk = min(total, max_det);
+      for (int t = tid; t < nk; t += kThreads) {
+        const unsigned rel = ~(unsigned)(keys[t] & 0xffffffffull);
+        const double* b = boxes + (size_t)(base + rel) * 4;
+        kept[t].x1 = b[0]; kept[t].y1 = b[1]; kept[t].x2 = b[2]; kept[t].y2 = b[3];
+        kept_rel[t] = rel;
+      }
+      __syncthreads();
+    } else {
+      // ---- 2. greedy walk
+      for (int pos = 0; pos < total && nk < max_det; pos += kThreads) {
+        const int c = pos + tid;
+        const bool valid = c < total;
+        Box b = {0.0, 0.0, 0.0, 0.0};
+        bool dead = !valid;
+        if (valid) {
+          const unsigned rel = ~(unsigned)(keys[c] & 0xffffffffull);
+          const double* p = boxes + (size_t)(base + rel) * 4;
+          b.x1 = p[0]; b.y1 = p[1]; b.x2 = p[2]; b.y2 = p[3];
+          const double ab = (b.x2 - b.x1) * (b.y2 - b.y1);
+          for (int j = 0; j < nk && !dead; ++j) dead = suppresses(kept[j], b, ab, thr);
+        }
+        chunk[tid] = b;
+        const unsigned long long alive_w = __ballot(!dead);
+        if (lane == 0) alive_mask[tid >> 6] = alive_w;
+        __syncthreads();
+        if (tid < 64) {
+          const int nk0 = nk;
+          int n = nk;
+          for (int s = 0; s < kWaves && n < max_det; ++s) {
+            unsigned long long alive = alive_mask[s];
+            if (alive == 0ull) continue;
+            const Box m = chunk[s * 64 + lane];
+            const double am = (m.x2 - m.x1) * (m.y2 - m.y1);
+            bool d = !((alive >> lane) & 1ull);
+            for (int j = nk0; j < n && !d; ++j) d = suppresses(kept[j], m, am, thr);     // kept since this chunk began
+            alive = __ballot(!d);
+            while (alive != 0ull) {
+              const int i = __ffsll((long long)alive) - 1;       // the first survivor is kept
+              const Box e = box_shfl(m, i);
+              if (lane == i) {
+                kept[n] = m;
+                kept_rel[n] = ~(unsigned)(keys[pos + s * 64 + lane] & 0xffffffffull);
+              }
+              ++n;
+              if (n >= max_det) break;
+              if (!d && lane > i) d = suppresses(e, m, am, thr);
+              alive = __ballot(!d) & ~(i == 63 ? ~0ull : ((2ull << i) - 1ull));
+            }
+          }
+          if (lane == 0) sh_nk = n;
+        }
+        __syncthreads();
+        nk = sh_nk;
+      }
+    }
+  }
+
+  // ---- 3. outputs
+  if (tid == 0) { out_count[img] = nk; out_status[img] = too_many ? 1 : 0; }
+  for (int t = tid; t < max_det; t += kThreads) {
+    if (t < nk) {
+      const long long flat = base + kept_rel[t];
+      const Box b = kept[t];
+      ob[t * 4] = b.x1; ob[t * 4 + 1] = b.y1; ob[t * 4 + 2] = b.x2; ob[t * 4 + 3] = b.y2;
+      os[t] = scores[flat];
+      oi[t] = (int32_t)flat;
+    } else {
+      ob[t * 4] = ob[t * 4 + 1] = ob[t * 4 + 2] = ob[t * 4 + 3] = 0.0;
+      os[t] = 0.f;
+      oi[t] = -1;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int mbx_merge_detections(const double* boxes, const float* scores, const int32_t* count,
+                                    const int32_t* image_rows, int I, int k_max, int max_det, double iou_threshold,
+                                    double* out_boxes, float* out_scores, int32_t* out_src, int32_t* out_count,
+                                    int32_t* out_status, mbx_stream_t stream) {
+  if (!boxes || !scores || !count || !image_rows || !out_boxes || !out_scores || !out_src || !out_count || !out_status)
+    return MBX_ERR_INVALID_ARG;
+  if (I < 0 || k_max <= 0 || max_det <= 0) return MBX_ERR_INVALID_ARG;
+  if (max_det > kMergeMaxDet) return MBX_ERR_UNSUPPORTED;
+  if (I == 0) return MBX_OK;
+  const size_t lds = (size_t)kMaxCand * sizeof(unsigned long long) + ((size_t)max_det + kThreads) * sizeof(Box) +
+                     (size_t)max_det * sizeof(unsigned);
+  const int use_iou = !(isinf(iou_threshold) && iou_threshold > 0.0);
+  MBX_ENTER();
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess) return MBX_ERR_LAUNCH;
+  hipLaunchKernelGGL(merge_kernel, dim3(I), dim3(kThreads), lds, mbx_s(stream), boxes, scores, count, image_rows, k_max,
+                     max_det, iou_threshold, use_iou, out_boxes, out_scores, out_src, out_count, out_status);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import records as REC
 
 
 def extract_patches(image, patch_dims, strides, non_edge_restriction=0.1):
@@ -103,6 +104,92 @@ def results_to_json_records(boxes, scores, count, image_ids):
 
 
 from .records import results_to_json_text, batch_chunk, records_to_json      # noqa: E402,F401  (torch-free: run in worker processes)
+
+
+# ----------------------------------------------------------------------------- per-image merge (not in the reference)
+class ImageMerger:
+    """All candidates of one image, from all its patches, ordered by score, de-duplicated by greedy NMS across patches and
+    cut to max_detections (mbx_merge_detections, one workgroup per image).  Fed with the HOST copies of the per-patch
+    stage's output, batch by batch in stream order -- the same path for one rank and for many; the rows of one image
+    are adjacent, an image may straddle batches.  iou_threshold None or inf: no suppression, top-N per image."""
+
+    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256):
+        self.K, self.max_det = int(k_max), int(max_detections)
+        self.thr = float("inf") if iou_threshold is None else float(iou_threshold)
+        self.device, self.flush_images = device, max(1, int(flush_images))
+        self.stream = torch.cuda.Stream(device=device)      # its uploads and launches do not queue behind the detect loop
+        self._rows, self._ids, self._runs = [], [], 0
+        self._out = []                                      # (ids, boxes, scores, count) per launch
+        self._warned = False
+
+    def add(self, boxes, scores, count, image_ids):
+        """boxes [B,K,4] f64, scores [B,K] f32, count [B] i32 (host arrays of one batch; copied), image_ids [B]."""
+        boxes, scores, count = (np.array(boxes, np.float64), np.array(scores, np.float32), np.array(count, np.int32))
+        assert boxes.shape == (len(count), self.K, 4) and scores.shape == (len(count), self.K) == (len(image_ids), self.K)
+        for i in image_ids:
+            if not self._ids or i != self._ids[-1]:
+                self._runs += 1
+            self._ids.append(i)
+        self._rows.append((boxes, scores, count))
+        if self._runs - 1 >= self.flush_images:             # every image but the one the stream is still in
+            self._flush(final=False)
+
+    def _flush(self, final):
+        if not self._ids:
+            return
+        ids, image_rows = REC.group_rows(self._ids)
+        n_img = len(ids) if final else len(ids) - 1
+        if n_img == 0:
+            return
+        end = int(image_rows[n_img])
+        boxes, scores, count = (np.concatenate([r[j] for r in self._rows]) for j in range(3))
+        self._rows = [(boxes[end:], scores[end:], count[end:])] if end < len(count) else []
+        self._ids, self._runs = self._ids[end:], len(ids) - n_img
+        ids, image_rows = ids[:n_img], image_rows[:n_img + 1].copy()
+        boxes, scores, count = boxes[:end], scores[:end], np.clip(count[:end], 0, self.K)
+        per_image = np.add.reduceat(np.concatenate([count, [0]]).astype(np.int64), image_rows[:-1])   # (no image is empty of rows)
+        if (per_image > REC.MERGE_MAX_CANDIDATES).any():
+            if not self._warned:
+                print("WARNING: an image has more than %d candidates; merging its best %d (warned once per run)"
+                      % (REC.MERGE_MAX_CANDIDATES, REC.MERGE_MAX_CANDIDATES), flush=True)
+                self._warned = True
+            parts, new_rows = [], [0]
+            for i in range(n_img):
+                a, b = int(image_rows[i]), int(image_rows[i + 1])
+                part = (boxes[a:b], scores[a:b], count[a:b])
+                if per_image[i] > REC.MERGE_MAX_CANDIDATES:
+                    part = REC.repack_rows(part[0], part[1], REC.best_candidates(part[1], part[2]), self.K)
+                parts.append(part)
+                new_rows.append(new_rows[-1] + len(part[2]))
+            boxes, scores, count = (np.concatenate([p[j] for p in parts]) for j in range(3))
+            image_rows = np.array(new_rows, np.int32)
+        assert len(count) * self.K < 2 ** 31
+        with torch.cuda.stream(self.stream):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            d_boxes, d_scores, d_count, d_rows = up(boxes), up(scores), up(count.astype(np.int32)), up(image_rows.astype(np.int32))
+            o_boxes = torch.empty((n_img, self.max_det, 4), dtype=torch.float64, device=self.device)
+            o_scores = torch.empty((n_img, self.max_det), dtype=torch.float32, device=self.device)
+            o_src = torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
+            o_count = torch.empty((n_img,), dtype=torch.int32, device=self.device)
+            o_status = torch.empty((n_img,), dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().mbx_merge_detections(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
+                                                       d_rows.data_ptr(), n_img, self.K, self.max_det, self.thr,
+                                                       o_boxes.data_ptr(), o_scores.data_ptr(), o_src.data_ptr(),
+                                                       o_count.data_ptr(), o_status.data_ptr(), self.stream.cuda_stream),
+                       "mbx_merge_detections")
+            status = o_status.cpu().numpy()
+            if status.any():
+                raise _lib.MbxError("mbx_merge_detections: status %d for image %r" % (int(status.max()), ids[int(np.argmax(status != 0))]))
+            self._out.append((ids, o_boxes.cpu().numpy(), o_scores.cpu().numpy(), o_count.cpu().numpy()))
+
+    def finish(self):
+        """Flush the rest (the last image included): (ids, boxes [N,max_det,4], scores [N,max_det], count [N]), images in
+        stream order, each image's detections in kept order."""
+        self._flush(final=True)
+        out, self._out = self._out, []
+        if not out:
+            return ([], np.zeros((0, self.max_det, 4), np.float64), np.zeros((0, self.max_det), np.float32), np.zeros((0,), np.int32))
+        return ([i for o in out for i in o[0]],) + tuple(np.concatenate([o[j] for o in out]) for j in (1, 2, 3))
 
 
 # ----------------------------------------------------------------------------- multi-GPU detect (SURVEY 8e)

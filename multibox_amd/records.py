@@ -30,6 +30,69 @@ def batch_chunk(boxes, scores, count, image_ids):
     return len(recs), ", ".join(recs)
 
 
+# ------------------------------------------------------------------ per-image merge (mbx_merge_detections): host side
+MERGE_MAX_CANDIDATES = 16384           # MBX_MERGE_MAX_CANDIDATES (include/mbx.h)
+
+
+def group_rows(image_ids):
+    """Runs of equal consecutive ids in stream order: (ids, image_rows [len(ids) + 1] int32); image i owns the rows
+    [image_rows[i], image_rows[i + 1]).  An id that returns later is a new image; the padding rows of a partial batch
+    carry the last image's id (and count 0), so they join it."""
+    ids, starts = [], []
+    for r, image_id in enumerate(image_ids):
+        if not ids or image_id != ids[-1]:
+            ids.append(image_id)
+            starts.append(r)
+    return ids, np.array(starts + [len(image_ids)], np.int32)
+
+
+def score_order_keys(scores):
+    """The order-preserving image of the float32 bits that the device sorts by (decode_filter_topk_kernel, merge_kernel):
+    uint32, larger = earlier; -0 == +0, a NaN above everything."""
+    s = np.ascontiguousarray(scores, np.float32)
+    u = s.view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    key = np.where(s == 0, np.uint32(0x80000000), key)
+    return np.where(np.isnan(s), np.uint32(0xffffffff), key).astype(np.uint32)
+
+
+def best_candidates(scores, count, limit=MERGE_MAX_CANDIDATES):
+    """Flat indices (row * K + slot, int64) of the best `limit` candidates of the rows scores [R,K] / count [R], in merge
+    order: score descending, ties by ascending flat index."""
+    scores, count = np.asarray(scores, np.float32), np.clip(np.asarray(count, np.int64), 0, scores.shape[1])
+    flat = np.flatnonzero(np.arange(scores.shape[1])[None, :] < count[:, None])
+    key = score_order_keys(scores.reshape(-1)[flat]).astype(np.int64)
+    return flat[np.argsort(-key, kind="stable")][:limit]
+
+
+def repack_rows(boxes, scores, flat, k_max):
+    """The candidates `flat` (best_candidates) of boxes [R,K,4] / scores [R,K] as fresh rows of k_max slots, in that
+    order -- what an image above the candidate limit is uploaded as.  Returns (boxes, scores, count)."""
+    n = len(flat)
+    rows = max(1, -(-n // k_max))
+    b, s = np.zeros((rows * k_max, 4), np.float64), np.zeros((rows * k_max,), np.float32)
+    b[:n], s[:n] = np.asarray(boxes).reshape(-1, 4)[flat], np.asarray(scores).reshape(-1)[flat]
+    count = np.clip(n - np.arange(rows) * k_max, 0, k_max).astype(np.int32)
+    return b.reshape(rows, k_max, 4), s.reshape(rows, k_max), count
+
+
+def compact_rows(boxes, scores, count):
+    """(count, valid boxes [n,4], valid scores [n]) of one batch: what a rank sends to rank 0 for the merge."""
+    boxes, scores = np.asarray(boxes), np.asarray(scores)
+    count = np.clip(np.asarray(count, np.int32), 0, scores.shape[1])
+    valid = np.arange(scores.shape[1])[None, :] < count[:, None]
+    return count.copy(), boxes[valid], scores[valid]
+
+
+def expand_rows(count, boxes, scores, k_max):
+    """Inverse of compact_rows: rows of k_max slots, unused slots zero."""
+    count = np.asarray(count, np.int32)
+    valid = np.arange(k_max)[None, :] < count[:, None]
+    b, s = np.zeros((len(count), k_max, 4), np.float64), np.zeros((len(count), k_max), np.float32)
+    b[valid], s[valid] = boxes, scores
+    return b, s, count
+
+
 def records_to_json(records):
     """The file detect.py:458-460 writes (json.dump of the record list) from record dicts, record strings or per-batch
     chunks of records (strings joined with ", "; empty chunks are skipped)."""

@@ -20,3 +20,31 @@ def synthetic_batch(batch, size=299, max_num_bboxes=13, seed=0):
 
 DEFAULT_ASPECT_RATIOS = {5: [1.0, 2.0, 3.0, 1.0 / 2.0, 1.0 / 3.0],
                          7: [1.0, 2.0, 3.0, 1.0 / 2.0, 1.0 / 3.0, 1.5, 1.0 / 1.5]}
+
+
+def merge_candidates(seed, I, rows_per_image, K, n_obj, tie_levels=64, unrelated=0.3, count=None):
+    """Seeded input of the per-image merge (mbx_merge_detections): I images of rows_per_image = (lo, hi) rows of K slots.
+    Every image has n_obj objects; a slot holds a jittered copy of one of them or, with probability `unrelated`, an
+    unrelated box; scores are quantised to 1 / tie_levels (ties in every image) and sorted within a row; `count` per row is
+    random in [0, K] (or the given constant).  Returns boxes [R,K,4] f64, scores [R,K] f32, count [R] i32, image_rows [I+1]."""
+    rng = np.random.RandomState(seed)
+    rows = rng.randint(rows_per_image[0], rows_per_image[1] + 1, I)
+    image_rows = np.concatenate([[0], np.cumsum(rows)]).astype(np.int32)
+    R = int(image_rows[-1])
+    boxes, scores = np.zeros((R, K, 4)), np.zeros((R, K), np.float32)
+    cnt = rng.randint(0, K + 1, R).astype(np.int32)
+    for i in range(I):
+        c, wh = rng.uniform(0.15, 0.85, (n_obj, 2)), rng.uniform(0.05, 0.3, (n_obj, 2))
+        for r in range(image_rows[i], image_rows[i + 1]):
+            o = rng.randint(0, n_obj, K)
+            jit = rng.normal(0, 0.01, (K, 4))
+            bx = np.clip(np.stack([c[o, 0] - wh[o, 0] / 2 + jit[:, 0], c[o, 1] - wh[o, 1] / 2 + jit[:, 1],
+                                   c[o, 0] + wh[o, 0] / 2 + jit[:, 2], c[o, 1] + wh[o, 1] / 2 + jit[:, 3]], 1), 0, 1)
+            rnd = rng.rand(K) < unrelated
+            rb = np.sort(rng.rand(K, 2, 2), axis=1).reshape(K, 4)[:, [0, 2, 1, 3]]
+            bx[rnd] = rb[rnd]
+            sc = (np.floor(rng.rand(K) * tie_levels) / tie_levels).astype(np.float32)
+            boxes[r], scores[r] = bx, -np.sort(-sc)
+    if count is not None:
+        cnt = np.broadcast_to(np.asarray(count, np.int32), (R,)).copy()
+    return boxes, scores, cnt, image_rows

@@ -656,6 +656,13 @@ inline void bn_fused_grid(long long M, int C, int rows, int& groups, int& chunks
 // HBM traffic 4 B read + 2 B written per element instead of 8 + 2, and one launch instead of three.
 // The grid is never larger than the CU count and one workgroup always fits a CU, so every workgroup is
 // resident and the barrier cannot deadlock; the spin is bounded all the same (error flag in the workspace).
+// In front of the atomics the workgroup adds up its own rows in LDS: lanes write their 16 sums as [rpi][2C] (the
+// accumulator's order), then ALL threads sum columns -- with 2C >= 512 thread t takes columns t, t + 512, ...; with
+// fewer columns than threads the rows are dealt to np = 512 / 2C row parts and 2C threads add the np partials -- with
+// 16 independent LDS reads in flight per thread, so the phase is a few LDS round trips whatever rpi is (it was one
+// per row on C/8 threads: up to 64 in a row for the narrow block35 layers).  The order of the additions inside a
+// workgroup is fixed by this geometry; across workgroups it is the arrival order of the atomics, as before.
+// Behind the barrier a lane reads its 16 totals with four 16-byte LDS reads, one round trip.
 #ifndef MBX_OB_SLOTS
 #define MBX_OB_SLOTS 8
 #endif
@@ -705,6 +712,43 @@ __device__ __forceinline__ void ob_store16(__amdgpu_buffer_rsrc_t r, unsigned by
   __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)byte_off, 0, 0);         // past the end -> dropped
 }
 
+// Column sums over LDS rows: t[k] = sum over r < nrows of p[k * cstride + r * rstride] for the k < ncols <= NC columns of a
+// thread, rows added in ascending order.  NC * NR independent reads are issued per LDS round trip; a read past the last
+// column / row is clamped onto a valid address and its value dropped, so a batch has no branches.
+template <int NC, int NR>
+__device__ __forceinline__ void ob_sum_cols(const float* p, int cstride, int ncols, int rstride, int nrows, float (&t)[NC]) {
+#pragma unroll
+  for (int k = 0; k < NC; ++k) t[k] = 0.f;
+  for (int r0 = 0; r0 < nrows; r0 += NR) {
+    float v[NC][NR];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const int ko = (k < ncols ? k : 0) * cstride;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) v[k][r] = p[ko + (r0 + r < nrows ? r0 + r : nrows - 1) * rstride];
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const bool in = r0 + r < nrows;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) t[k] += in ? v[k][r] : 0.f;
+    }
+  }
+}
+
+// 2C >= kObT: thread t owns columns t, t + kObT, ... of the workgroup's [rpi][2C] sums and adds each column's total to acc
+template <int NC, int NR>
+__device__ __forceinline__ void ob_reduce_wide(const float* rows, int C2, int rpi, float* acc) {
+  for (int e0 = threadIdx.x; e0 < C2; e0 += NC * kObT) {
+    const int ncols = (C2 - e0 + kObT - 1) / kObT;                   // >= 1; more than NC: the next trip takes the rest
+    float t[NC];
+    ob_sum_cols<NC, NR>(rows + e0, kObT, ncols, C2, rpi, t);
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+      if (k < ncols) atomicAdd(acc + e0 + k * kObT, t[k]);
+  }
+}
+
 template <int NV, bool RELU>
 __global__ void __launch_bounds__(kObT)
 bn_bwd_onepass_kernel(const unsigned short* __restrict__ da, int ld_da, const unsigned short* __restrict__ y,
@@ -712,7 +756,7 @@ bn_bwd_onepass_kernel(const unsigned short* __restrict__ da, int ld_da, const un
                       const float* __restrict__ beta, float* __restrict__ dbeta, unsigned short* __restrict__ dy,
                       float* __restrict__ ws, int rpi, int rpb, float inv_M, unsigned spin_limit, int fault,
                       float* __restrict__ step_poison, const ChanMap map, int map_max) {
-  extern __shared__ __attribute__((aligned(16))) float sred[];   // [rpi][C8][16] partial sums, then [2C] totals
+  extern __shared__ __attribute__((aligned(16))) float sred[];   // [rpi][2C] partial sums + row parts, then [2C] totals
   __shared__ int s_timeout;                                      // this workgroup gave up on the grid barrier
   const int C8 = C >> 3;
   const int vc = threadIdx.x % C8, rr = threadIdx.x / C8;
@@ -773,31 +817,41 @@ bn_bwd_onepass_kernel(const unsigned short* __restrict__ da, int ld_da, const un
     asm volatile("" : "+v"(s1[0]), "+v"(s1[1]), "+v"(s1[2]), "+v"(s1[3]), "+v"(s1[4]), "+v"(s1[5]), "+v"(s1[6]), "+v"(s1[7]));
     asm volatile("" : "+v"(s2[0]), "+v"(s2[1]), "+v"(s2[2]), "+v"(s2[3]), "+v"(s2[4]), "+v"(s2[5]), "+v"(s2[6]), "+v"(s2[7]));
   }
+  // each lane's sums go to row rr of sred[rpi][2C] in the accumulator's order: s1 of all channels, then s2
+  const int C2 = 2 * C;
   if (active) {
-    float* o = sred + ((size_t)rr * C8 + vc) * 16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { o[j] = s1[j]; o[8 + j] = s2[j]; }
+    float4* o1 = reinterpret_cast<float4*>(sred + (size_t)rr * C2 + c);
+    float4* o2 = reinterpret_cast<float4*>(sred + (size_t)rr * C2 + C + c);
+    o1[0] = make_float4(s1[0], s1[1], s1[2], s1[3]); o1[1] = make_float4(s1[4], s1[5], s1[6], s1[7]);
+    o2[0] = make_float4(s2[0], s2[1], s2[2], s2[3]); o2[1] = make_float4(s2[4], s2[5], s2[6], s2[7]);
   }
   __syncthreads();
   float* acc = ws + (size_t)(blockIdx.x & (kObSlots - 1)) * 2 * C;
   unsigned* ctl = reinterpret_cast<unsigned*>(ws + (size_t)kObSlots * 2 * C);
-  if (threadIdx.x < C8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    for (int r = 0; r < rpi; ++r) {
-      const float* o = sred + ((size_t)r * C8 + threadIdx.x) * 16;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { s1[j] += o[j]; s2[j] += o[8 + j]; }
-    }
-    // stage the workgroup's sums as [2][C] behind the partials, so that the atomics below are lane-contiguous
-    float* t = sred + (size_t)rpi * C8 * 16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { t[(threadIdx.x << 3) + j] = s1[j]; t[C + (threadIdx.x << 3) + j] = s2[j]; }
-  }
-  __syncthreads();
-  // one wave instruction = 64 consecutive floats: the memory-side atomic unit serialises per instruction and
+  // Column-parallel reduction of the rpi rows: every thread sums whole columns, 16 independent LDS reads per round trip,
+  // in an order fixed by the geometry.  Each column total goes from its register straight into the atomic.
+  // One wave instruction = 64 consecutive floats: the memory-side atomic unit serialises per instruction and
   // line (~24 ns each, measured: tools/atomic_bench.hip), so the layout decides the cost, not the lane count
-  for (int e = threadIdx.x; e < 2 * C; e += kObT) atomicAdd(acc + e, sred[(size_t)rpi * C8 * 16 + e]);
+  const int np = C2 < kObT ? kObT / C2 : 1;                  // row parts when there are fewer columns than threads
+  if (np > 1) {                                              // (workgroup-uniform: the barrier inside is reached by all)
+    // thread (e, p) sums rows p, p + np, ... of column e into part[p][e] behind the rows; threads < 2C add the np parts
+    float* part = sred + (size_t)rpi * C2;
+    const int e = threadIdx.x % C2, p = threadIdx.x / C2;
+    float t[1];
+    if (p < np) {
+      ob_sum_cols<1, 16>(sred + p * C2 + e, 0, 1, np * C2, (rpi - p + np - 1) / np, t);
+      part[p * C2 + e] = t[0];
+    }
+    __syncthreads();
+    if (threadIdx.x < C2) {
+      ob_sum_cols<1, 16>(part + threadIdx.x, 0, 1, C2, np, t);
+      atomicAdd(acc + threadIdx.x, t[0]);
+    }
+  } else if (rpi > 8) ob_reduce_wide<1, 16>(sred, C2, rpi, acc);     // (rpi * 2C <= 16 * kObT: one round trip per thread
+  else if (rpi > 4) ob_reduce_wide<2, 8>(sred, C2, rpi, acc);        //  in all of these, but for a ragged last column)
+  else if (rpi > 2) ob_reduce_wide<4, 4>(sred, C2, rpi, acc);
+  else if (rpi > 1) ob_reduce_wide<8, 2>(sred, C2, rpi, acc);
+  else ob_reduce_wide<16, 1>(sred, C2, rpi, acc);
   // ---- grid barrier.  Everything that is polled or counted sits on its own 128-byte line and is shared by few
   // workgroups (the same 24 ns per access apply): arrivals go to kObSub counters, the last arrival of each to
   // the top counter, the last of those sets kObRel release words; workgroup b polls release word b % kObRel.
@@ -843,18 +897,34 @@ bn_bwd_onepass_kernel(const unsigned short* __restrict__ da, int ld_da, const un
     sred[e] = t;
   }
   __syncthreads();
-  float m1[8], m2[8];
+  float m1[8], m2[8], t1[8];
   const float poison = s_timeout ? __builtin_nanf("") : 0.f;
+  {
+    // the 16 totals of a lane in ONE LDS round trip: four 16-byte reads (c is a multiple of 8: 32-byte aligned).  The empty
+    // asm keeps them whole: without it the compiler splits them into 4- and 8-byte reads, the first one behind a branch
+    const float* tot = sred + (active ? c : 0);
+    u32x4 p0 = *reinterpret_cast<const u32x4*>(tot), p1 = *reinterpret_cast<const u32x4*>(tot + 4);
+    u32x4 q0 = *reinterpret_cast<const u32x4*>(tot + C), q1 = *reinterpret_cast<const u32x4*>(tot + C + 4);
+    asm volatile("" : "+v"(p0), "+v"(p1), "+v"(q0), "+v"(q1));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      t1[j] = __uint_as_float(p0[j]); t1[4 + j] = __uint_as_float(p1[j]);
+      m2[j] = __uint_as_float(q0[j]); m2[4 + j] = __uint_as_float(q1[j]);
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float t1 = (active ? sred[c + j] : 0.f) + poison;
-    m1[j] = t1 * inv_M;
-    m2[j] = (active ? sred[C + c + j] : 0.f) * inv_M;
-    // d(beta) += sum g, by workgroup 0: a fire-and-forget atomic add (one adder per address: the same float as `+=`).  As
-    // `dbeta[c + j] += t1` it compiled to eight load -> wait -> add -> store round trips IN A ROW on workgroup 0's first lanes --
-    // and a launch ends when its last workgroup does: 4-6 us on the tail of every one of the step's 141 launches (round 6,
-    // seen in the ISA: eight `s_waitcnt vmcnt(0)` behind the barrier).
-    if (blockIdx.x == 0 && rr == 0 && dbeta) atomicAdd(dbeta + c + j, t1);
+    t1[j] = (active ? t1[j] : 0.f) + poison;
+    m1[j] = t1[j] * inv_M;
+    m2[j] = (active ? m2[j] : 0.f) * inv_M;
+  }
+  // d(beta) += sum g, by workgroup 0: fire-and-forget atomic adds from the registers (one adder per address: the same float as
+  // `+=`).  As `dbeta[c + j] += t1` it compiled to eight load -> wait -> add -> store round trips IN A ROW on workgroup 0's
+  // first lanes -- and a launch ends when its last workgroup does: 4-6 us on the tail of every one of the step's 141
+  // launches (round 6, seen in the ISA: eight `s_waitcnt vmcnt(0)` behind the barrier).
+  if (blockIdx.x == 0 && rr == 0 && dbeta) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) atomicAdd(dbeta + c + j, t1[j]);
   }
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -1853,7 +1923,7 @@ extern "C" int mbx_bn_bwd_onepass_mapped(const void* da, int ld_da, int relu, co
   const ObGeom g = ob_geom(M, C, ncu);
   if (g.nv > kObMaxNV) return MBX_ERR_UNSUPPORTED;
   MBX_ENTER();
-  const size_t lds = ((size_t)g.rpi * g.C8 * 16 + (size_t)2 * C) * sizeof(float);
+  const size_t lds = ((size_t)g.rpi * 2 * C + (size_t)(2 * C > kObT ? 2 * C : kObT)) * sizeof(float);   // rows + row parts
   static int fault = -1;
   if (fault < 0) { const char* e = getenv("MBX_DEBUG_BARRIER_FAULT"); fault = (e && e[0] == '1') ? 1 : 0; }
   const unsigned spin_limit = fault ? (1u << 10) : (1u << 22);

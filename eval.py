@@ -23,6 +23,8 @@ def parse_args():
     p.add_argument("--checkpoint_path", dest="checkpoint_path", type=str, required=True)
     p.add_argument("--config", dest="config_file", type=str, required=True)
     p.add_argument("--max_iterations", dest="max_iterations", type=int, default=0)
+    p.add_argument("--device_metric", dest="device_metric", action="store_true",
+                   help="match detections to ground truth on the GPU (mbx_coco_match); the same twelve numbers")
     return p.parse_args()
 
 
@@ -32,7 +34,7 @@ def main():
     import torch
     from multibox_amd.config import parse_config_file, with_defaults
     from multibox_amd import priors as PR, checkpoint as CK, detect as D, _lib
-    from multibox_amd.cocoeval import evaluate_bbox
+    from multibox_amd.cocoeval import evaluate_bbox, evaluate_bbox_device
     from multibox_amd.engine import Net
     from multibox_amd.inputs import eval_batches
     import __graft_entry__ as g
@@ -103,7 +105,7 @@ def main():
         print("Step: %d, Time/image (ms): %.1f" % (step, dt / B * 1000))
         if args.max_iterations > 0 and step == args.max_iterations:
             break
-    stats, lines = evaluate_bbox(gt_annotations, pred_annotations)
+    stats, lines = (evaluate_bbox_device if args.device_metric else evaluate_bbox)(gt_annotations, pred_annotations)
     out = {}
     for line in lines:
         print(line)
@@ -112,7 +114,8 @@ def main():
     os.makedirs(args.summary_dir, exist_ok=True)
     path = os.path.join(args.summary_dir, "eval-%d.json" % global_step)
     with open(path, "w") as f:
-        json.dump({"global_step": global_step, "images": step * B, "stats": stats, "summary": out}, f, indent=1)
+        json.dump({"global_step": global_step, "images": step * B, "stats": stats, "summary": out,
+                   "metric_path": "device" if args.device_metric else "host"}, f, indent=1)
     print("wrote", path)
 
 

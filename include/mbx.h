@@ -140,6 +140,34 @@ int mbx_merge_detections(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const 
                          float* out_scores /*[I,max_det]*/, int32_t* out_src /*[I,max_det]*/,
                          int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/, mbx_stream_t stream);
 
+/* ------------------------------------------------------ COCO metric: matching (eval.py:212-226)
+ * Replaces the matching step of the metric eval.py:212-226 runs: pycocotools' COCOeval.evaluateImg (iouType 'bbox',
+ * useCats = 0, no crowd annotations), once per image, area range and IoU threshold; multibox_amd/cocoeval.py:_evaluate_img
+ * restates it and is the definition.  Image i owns detections [dt_rows[i], dt_rows[i+1]) -- ALREADY in evaluation order
+ * (score descending, stable) and cut to MBX_COCO_MAX_DET -- and gts [gt_rows[i], gt_rows[i+1]) in annotation order.
+ * Per (image, range [a0, a1], threshold t): the gts are taken with the in-range ones (a0 <= area <= a1, the annotation's
+ * area column) first, stably; each detection in order takes, among the gts no earlier detection took, the in-range one
+ * with the largest IoU >= min(t, 1 - 1e-10), of equal IoUs the later; only if there is none, the same among the
+ * out-of-range ones.  IoU in float64 in the operation order of cocoeval._iou_xywh (x1 = x + w; iw = max(min - max, 0);
+ * union = (dw*dh + gw*gh) - inter; union > 0 ? inter / union : 0), so every comparison is the host's.  iou_thrs and
+ * area_rng are HOST arrays, read before the call returns (pass cocoeval.IOU_THRS: np.linspace's values are part of the
+ * parity).  All inputs must be finite.
+ *   match[i,a,t,d]   the gt's row within its image in ANNOTATION order, or -1
+ *   ignore[i,a,t,d]  1 iff the matched gt is out of range, or d is unmatched and its own area w*h is < a0 or > a1
+ *   n_gt_counted[i,a] number of in-range gts
+ *   slots d past the image's detections: -1 / 0
+ *   status[i]        0 ok; 1 = more than MBX_COCO_MAX_GT gts or MBX_COCO_MAX_DET detections: outputs -1 / 0 / 0, the
+ *                    caller computes that image on the host
+ * I == 0: MBX_OK, nothing launched.  T outside [1,16] or A outside [1,8]: MBX_ERR_INVALID_ARG.  One workgroup per image,
+ * one wavefront per threshold.                                                                                        */
+#define MBX_COCO_MAX_DET 100
+#define MBX_COCO_MAX_GT 128
+int mbx_coco_match(const double* dt /*[ND,5] x,y,w,h,score*/, const int32_t* dt_rows /*[I+1] ascending*/,
+                   const double* gt /*[NG,5] x,y,w,h,area*/, const int32_t* gt_rows /*[I+1] ascending*/, int I,
+                   const double* iou_thrs /*HOST [T], T <= 16*/, int T, const double* area_rng /*HOST [A,2], A <= 8*/,
+                   int A, int16_t* match /*[I,A,T,MBX_COCO_MAX_DET]*/, uint8_t* ignore /*[I,A,T,MBX_COCO_MAX_DET]*/,
+                   int32_t* n_gt_counted /*[I,A]*/, int32_t* status /*[I]*/, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ convolution stack (A2-A4)
  * Replaces slim.conv2d (+ batch_norm + relu) of model.py:6-324 and its TF gradients
  * (train.py:263).  Activations are NHWC bf16 *views*: element (n,h,w,c) of a tensor lives at

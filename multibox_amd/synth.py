@@ -48,3 +48,38 @@ def merge_candidates(seed, I, rows_per_image, K, n_obj, tie_levels=64, unrelated
     if count is not None:
         cnt = np.broadcast_to(np.asarray(count, np.int32), (R,)).copy()
     return boxes, scores, cnt, image_rows
+
+
+def coco_eval_set(seed, I, n_gt=(0, 13), n_dt=(0, 130), size=299, quantum=0.5, score_levels=8, counts=None):
+    """Seeded input of the COCO metric (cocoeval.evaluate_bbox / evaluate_bbox_device): I images in a size-pixel frame with
+    n_gt = (lo, hi) ground-truth boxes (sides from a few pixels to most of the frame, so every area range is met) and
+    n_dt = (lo, hi) detections: jittered copies of the image's gts and, for one in three (or without gts), random boxes.
+    Coordinates are multiples of `quantum` pixels and scores take `score_levels` distinct values (0 = continuous scores),
+    so IoU ties and score ties occur (one gt in seven
+    repeats an earlier one of its image).  `counts`: the (gts, detections) of each image instead of random ones.  Returns (gt_annotations, pred_annotations) as eval.py builds them."""
+    rng = np.random.RandomState(seed)
+    q = lambda v: np.round(np.asarray(v, np.float64) / quantum) * quantum
+    gts, dts = [], []
+    for i in range(I):
+        img_id = 1000 + 3 * i
+        ng, nd = rng.randint(n_gt[0], n_gt[1] + 1), rng.randint(n_dt[0], n_dt[1] + 1)
+        if counts is not None:
+            ng, nd = counts[i]
+        wh = q(np.exp(rng.uniform(np.log(4.0), np.log(0.8 * size), (ng, 2))))
+        xy = q(rng.uniform(0, 1, (ng, 2)) * (size - wh))
+        for j in range(1, ng):
+            if rng.rand() < 0.15:                                         # the same object annotated twice: equal IoUs
+                o = rng.randint(j)
+                xy[j], wh[j] = xy[o], wh[o]
+        for (x, y), (w, h) in zip(xy.tolist(), wh.tolist()):
+            gts.append({"id": len(gts) + 1, "image_id": img_id, "category_id": 1, "area": w * h, "bbox": [x, y, w, h], "iscrowd": 0})
+        for _ in range(nd):
+            if ng and rng.rand() < 2.0 / 3.0:
+                o = rng.randint(ng)
+                x, y, w, h = q(np.concatenate([xy[o], wh[o]]) + rng.choice([-2.0, -0.5, 0.0, 0.0, 0.5, 2.0], 4) * np.tile(wh[o], 2) / 16)
+            else:
+                w, h = q(np.exp(rng.uniform(np.log(4.0), np.log(0.8 * size), 2)))
+                x, y = q(rng.uniform(0, 1, 2) * (size - np.array([w, h])))
+            s = (1 + rng.randint(score_levels)) / (score_levels + 1.0) if score_levels else rng.rand()
+            dts.append([img_id, float(x), float(y), float(max(w, quantum)), float(max(h, quantum)), float(s), 1])
+    return gts, dts

@@ -2,7 +2,8 @@
 """Drop-in for the reference's eval.py (eval.py:248-305): same flags.  Forward pass in inference mode with the EMA
 weights (eval.py:46-76), decode + clip + top-100 on the GPU (eval.py:144-173 -> mbx_decode_filter_topk with
 whole-image metadata), boxes scaled to INPUT_SIZE pixels, then COCO bbox AP/AR with useCats = 0 (eval.py:212-226;
-multibox_amd/cocoeval.py restates pycocotools' COCOeval, which is not installed here).  The twelve summary numbers are
+multibox_amd/cocoeval.py restates pycocotools' COCOeval, which is not installed here; --device_metric runs both of its
+halves, the matching and the accumulation, on the GPU and prints the same numbers).  The twelve summary numbers are
 printed in COCOeval's format and written to <summary_dir>/eval-<global_step>.json (the reference writes a TF event
 file, eval.py:228-246)."""
 import argparse
@@ -24,7 +25,8 @@ def parse_args():
     p.add_argument("--config", dest="config_file", type=str, required=True)
     p.add_argument("--max_iterations", dest="max_iterations", type=int, default=0)
     p.add_argument("--device_metric", dest="device_metric", action="store_true",
-                   help="match detections to ground truth on the GPU (mbx_coco_match); the same twelve numbers")
+                   help="match detections to ground truth and accumulate precision / recall on the GPU (mbx_coco_match, "
+                        "mbx_coco_accumulate); the same twelve numbers")
     return p.parse_args()
 
 

@@ -168,6 +168,46 @@ int mbx_coco_match(const double* dt /*[ND,5] x,y,w,h,score*/, const int32_t* dt_
                    int A, int16_t* match /*[I,A,T,MBX_COCO_MAX_DET]*/, uint8_t* ignore /*[I,A,T,MBX_COCO_MAX_DET]*/,
                    int32_t* n_gt_counted /*[I,A]*/, int32_t* status /*[I]*/, mbx_stream_t stream);
 
+/* ------------------------------------------------------ COCO metric: accumulation (eval.py:227-246)
+ * Replaces the accumulation step of the same metric: pycocotools' COCOeval.accumulate for one category, on the outputs of
+ * mbx_coco_match; multibox_amd/cocoeval.py:accumulate_tables restates it and is the definition.  dt and dt_rows are the
+ * ones given to mbx_coco_match, under the same PRECONDITION: per image the detections are by score descending, stable,
+ * cut to MBX_COCO_MAX_DET (so an image's slot k never sorts before its slot k-1, and the first detection of the global
+ * order has slot 0).  match / ignore / n_gt_counted are what mbx_coco_match wrote (a refused image's rows filled in by the
+ * caller); of match only `>= 0` is read, of ignore only `!= 0`.  ND = dt_rows[I] is read from the device before anything
+ * is launched (one 4-byte copy and a wait on `stream`): the grids depend on it.
+ * The detections are ordered by score descending, ties by ascending row of dt (-0.0 == +0.0), which is
+ * argsort(-score, kind="mergesort").  For maxDets value max_dets[m] a detection takes part iff its slot within its image
+ * is < max_dets[m].  Per slice (t, a, m), over the detections that take part, in that order, with
+ * npig = sum_i n_gt_counted[i,a]:
+ *   tp[k] = number of k' <= k with match >= 0 and not ignore      fp[k] = ... with match < 0 and not ignore
+ *   rc[k] = tp[k] / npig      pr[k] = max over k' >= k of tp[k'] / ((fp[k'] + tp[k']) + 2.220446049250313e-16)
+ *   precision[t,r,a,m] = pr at the first k with rc[k] >= rec_thrs[r], 0 if there is none
+ *   recall[t,a,m]      = rc at the last k, 0 if no detection takes part
+ * in float64 in exactly this operation order, so the values are the host's bit for bit.  npig == 0: the slice's entries
+ * are -1.  rec_thrs and max_dets are HOST arrays, read before the call returns (pass cocoeval.REC_THRS: np.linspace's
+ * values are part of the parity).  I == 0: MBX_OK, both tables -1, nothing else launched.
+ * Limits: T in [1,16], A in [1,8] (mbx_coco_match's), R in [1,MBX_COCO_ACC_MAX_R], M in [1,MBX_COCO_ACC_MAX_M], a null
+ * pointer or workspace_bytes < mbx_coco_accumulate_workspace(ND, T, A, M): MBX_ERR_INVALID_ARG.  ND >
+ * MBX_COCO_ACC_MAX_ND: MBX_ERR_UNSUPPORTED.  Either way nothing is written and no detection is read.
+ * Workspace (no state survives a call; 256-byte aligned): with W = ceil(T A / 32) and S = T A M,
+ * ND (24 + 8 W + 1) bytes for the sort's two (key, index) buffers and the gathered flag bits, plus
+ * 16 S (ceil(ND / MBX_COCO_ACC_CHUNK) + 1) bytes of per-chunk totals and maxima, plus rounding: at most 89 bytes per
+ * detection (T = 16, A = 8, M = 4), 48.5 for COCO's 10 / 4 / 3.  mbx_coco_accumulate_workspace is host-only and returns
+ * 0 for sizes outside the limits.  Separate launches on `stream` (tile sort of MBX_COCO_ACC_SORT_TILE elements, merge
+ * passes, gather, chunk totals, their scan, chunk maxima, their suffix maximum, search); no workgroup waits on another. */
+#define MBX_COCO_ACC_MAX_R 128
+#define MBX_COCO_ACC_MAX_M 4
+#define MBX_COCO_ACC_MAX_ND 4194304
+#define MBX_COCO_ACC_CHUNK 256
+#define MBX_COCO_ACC_SORT_TILE 1024
+size_t mbx_coco_accumulate_workspace(long long ND, int T, int A, int M);
+int mbx_coco_accumulate(const double* dt /*[ND,5] x,y,w,h,score*/, const int32_t* dt_rows /*[I+1] ascending*/, int I,
+                        const int16_t* match /*[I,A,T,MBX_COCO_MAX_DET]*/, const uint8_t* ignore /*[I,A,T,MBX_COCO_MAX_DET]*/,
+                        const int32_t* n_gt_counted /*[I,A]*/, int T, int A, const double* rec_thrs /*HOST [R]*/, int R,
+                        const int32_t* max_dets /*HOST [M]*/, int M, double* precision /*[T,R,A,M]*/,
+                        double* recall /*[T,A,M]*/, void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ convolution stack (A2-A4)
  * Replaces slim.conv2d (+ batch_norm + relu) of model.py:6-324 and its TF gradients
  * (train.py:263).  Activations are NHWC bf16 *views*: element (n,h,w,c) of a tensor lives at

@@ -22,6 +22,7 @@ SOURCES = {
     "postproc.hip": ["-ffp-contract=off"],
     "merge.hip": ["-ffp-contract=off"],
     "cocomatch.hip": ["-ffp-contract=off"],
+    "cocoaccum.hip": ["-ffp-contract=off"],
     "conv.hip": ["-munsafe-fp-atomics"],
     # (the atomic optimizer turns the tile-fetch atomicAdd of conv_igemm5_kernel into scan + v_readfirstlane of the result,
     # i.e. waits for it at the issue; without it the wait sits where the value is published)

@@ -139,11 +139,17 @@ def evaluate_bbox(gt_annotations, pred_annotations):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The same metric with the matching on the GPU (mbx_coco_match, include/mbx.h) and a vectorised accumulation:
-# evaluate_bbox_device = pack -> match_device -> accumulate.  evaluate_bbox above stays the oracle; every array here holds
-# exactly the float64 values it builds, the kernel returns small integers, and the twelve numbers come out bit for bit.
+# The same metric with the matching and the accumulation on the GPU (mbx_coco_match, mbx_coco_accumulate, include/mbx.h):
+# evaluate_bbox_device = pack -> match_device(on_device=True) -> accumulate_device -> _summarize.  evaluate_bbox above stays
+# the oracle and the vectorised numpy accumulate_tables the reference of the device tables (and the path for sizes the
+# kernels refuse); every array here holds exactly the float64 values evaluate_bbox builds, the kernels work on integers
+# and repeat its divisions, and the twelve numbers come out bit for bit.
 MAX_DET = 100                                                             # MBX_COCO_MAX_DET == MAX_DETS[-1]
 MAX_GT = 128                                                              # MBX_COCO_MAX_GT
+ACC_MAX_ND = 4194304                                                      # MBX_COCO_ACC_MAX_ND
+ACC_CHUNK = 256                                                           # MBX_COCO_ACC_CHUNK
+ACC_SORT_TILE = 1024                                                      # MBX_COCO_ACC_SORT_TILE
+MBX_ERR_UNSUPPORTED = -2
 
 Packed = collections.namedtuple("Packed", "img_ids dt dt_rows gt gt_rows")
 
@@ -211,10 +217,11 @@ def _match_rows(dt, gt, a_rng):
     return rows
 
 
-def match_device(packed):
+def match_device(packed, on_device=False):
     """mbx_coco_match on the current device: match [I,A,T,MAX_DET] int16 (gt row in annotation order or -1), ignore uint8,
     n_gt_counted [I,A] int32.  Images the kernel refuses (status 1: more than MAX_GT gts) come from match_host; input
-    that is not finite goes to match_host altogether."""
+    that is not finite goes to match_host altogether.  on_device: the three as device tensors, without the download
+    (only the status and the refused images' rows cross the bus); numpy arrays still where the host computed everything."""
     I, A, T = len(packed.img_ids), len(AREA_RNG), len(IOU_THRS)
     if not (np.isfinite(packed.dt).all() and np.isfinite(packed.gt).all()):
         print("WARNING: non-finite box or score: COCO matching runs on the host", file=sys.stderr, flush=True)
@@ -241,6 +248,20 @@ def match_device(packed):
                                          thrs.ctypes.data, T, rng.ctypes.data, A, o_m.data_ptr(), o_i.data_ptr(),
                                          o_n.data_ptr(), o_s.data_ptr(), torch.cuda.current_stream().cuda_stream),
                "mbx_coco_match")
+    if on_device:
+        refused = np.nonzero(o_s.cpu().numpy())[0]
+        if len(refused):                                                  # the kernel wrote -1 / 0 / 0 for these
+            matched, h_ig, h_n = match_host(packed, refused)
+            rows = -np.ones((len(refused), A, T, MAX_DET), np.int16)
+            for k, i in enumerate(refused):
+                d, g = _image(packed, i)
+                for ai, a_rng in enumerate(AREA_RNG):
+                    rows[k, ai, :, :len(d)] = _rows_checked(d, g, a_rng, matched[i, ai, :, :len(d)])
+            where = torch.from_numpy(refused.astype(np.int64)).cuda()
+            o_m[where] = torch.from_numpy(rows).cuda()
+            o_i[where] = torch.from_numpy(np.ascontiguousarray(h_ig[refused])).cuda()
+            o_n[where] = torch.from_numpy(np.ascontiguousarray(h_n[refused])).cuda()
+        return o_m, o_i, o_n
     match, ignore, n_gt_counted, status = (t.cpu().numpy() for t in (o_m, o_i, o_n, o_s))
     refused = np.nonzero(status)[0]
     if len(refused):
@@ -282,9 +303,10 @@ def _summarize(precision, recall):
     return [v for v, _ in out], [line for _, line in out]
 
 
-def accumulate(packed, matched, ignore, n_gt_counted):
-    """The second half of evaluate_bbox (COCOeval.accumulate + summarize) on the arrays of match_host / match_device
-    (`matched` bool, or the int16 `match` whose >= 0 it is): the same sort, sums and divisions, so the same twelve floats."""
+def accumulate_tables(packed, matched, ignore, n_gt_counted):
+    """COCOeval.accumulate on the arrays of match_host / match_device (`matched` bool, or the int16 `match` whose >= 0 it
+    is): precision [T,R,A,M] and recall [T,A,M], by the same sort, sums and divisions as evaluate_bbox.  The definition
+    and oracle of mbx_coco_accumulate."""
     matched = np.asarray(matched)
     if matched.dtype != bool:
         matched = matched >= 0
@@ -320,10 +342,70 @@ def accumulate(packed, matched, ignore, n_gt_counted):
                 q = np.zeros(R)
                 q[ok] = pr[ti, inds[ok]]
                 precision[ti, :, ai, mi] = q
-    return _summarize(precision, recall)
+    return precision, recall
+
+
+def accumulate(packed, matched, ignore, n_gt_counted):
+    """The second half of evaluate_bbox (COCOeval.accumulate + summarize) on the arrays of match_host / match_device: the
+    same twelve floats."""
+    return _summarize(*accumulate_tables(packed, matched, ignore, n_gt_counted))
+
+
+class AccumulateUnsupported(Exception):
+    """mbx_coco_accumulate returned MBX_ERR_UNSUPPORTED (more than ACC_MAX_ND detections)."""
+
+
+def accumulate_device(packed, match, ignore, n_gt_counted):
+    """accumulate_tables by mbx_coco_accumulate on the current device: (precision, recall) as numpy arrays, bit for bit.
+    match / ignore / n_gt_counted are match_device's outputs, device tensors (on_device=True) or numpy arrays."""
+    import torch
+    from . import _lib
+    I, A, T = len(packed.img_ids), len(AREA_RNG), len(IOU_THRS)
+    R, M = len(REC_THRS), len(MAX_DETS)
+    nd = int(packed.dt_rows[-1]) if I else 0
+    assert len(packed.dt) == nd
+
+    def dev(a, dtype):
+        if isinstance(a, torch.Tensor):
+            assert a.is_cuda and a.dtype == dtype and a.is_contiguous()
+            return a if a.numel() else torch.zeros(1, dtype=dtype, device="cuda")
+        a = np.ascontiguousarray(a)
+        if a.dtype == bool and dtype == torch.int16:                      # match_host's `matched`
+            a = np.where(a, 0, -1).astype(np.int16)
+        t = torch.from_numpy(a.reshape(-1) if a.size else np.zeros(1, a.dtype))
+        assert t.dtype == dtype
+        return t.cuda()
+    d_m, d_i, d_n = dev(match, torch.int16), dev(ignore, torch.uint8), dev(n_gt_counted, torch.int32)
+    assert d_m.numel() >= I * A * T * MAX_DET and d_i.numel() >= I * A * T * MAX_DET and d_n.numel() >= I * A
+    d_dt, d_dr = dev(packed.dt, torch.float64), dev(packed.dt_rows, torch.int32)
+    l = _lib.lib()
+    ws_bytes = l.mbx_coco_accumulate_workspace(nd, T, A, M)
+    if nd > ACC_MAX_ND:
+        raise AccumulateUnsupported("%d detections > %d" % (nd, ACC_MAX_ND))
+    if ws_bytes == 0:
+        raise _lib.MbxError("mbx_coco_accumulate_workspace refuses ND=%d T=%d A=%d M=%d" % (nd, T, A, M))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    o_p = torch.empty((T, R, A, M), dtype=torch.float64, device="cuda")
+    o_r = torch.empty((T, A, M), dtype=torch.float64, device="cuda")
+    thrs = np.ascontiguousarray(REC_THRS, np.float64)
+    mds = np.ascontiguousarray(MAX_DETS, np.int32)
+    rc = l.mbx_coco_accumulate(d_dt.data_ptr(), d_dr.data_ptr(), I, d_m.data_ptr(), d_i.data_ptr(), d_n.data_ptr(), T, A,
+                               thrs.ctypes.data, R, mds.ctypes.data, M, o_p.data_ptr(), o_r.data_ptr(), ws.data_ptr(),
+                               ws_bytes, torch.cuda.current_stream().cuda_stream)
+    if rc == MBX_ERR_UNSUPPORTED:
+        raise AccumulateUnsupported("mbx_coco_accumulate: unsupported size")
+    _lib.check(rc, "mbx_coco_accumulate")
+    return o_p.cpu().numpy(), o_r.cpu().numpy()
 
 
 def evaluate_bbox_device(gt_annotations, pred_annotations):
-    """evaluate_bbox with the matching on the GPU: the same twelve floats and lines."""
+    """evaluate_bbox with the matching and the accumulation on the GPU: the same twelve floats and lines.  Non-finite
+    input takes the host path altogether; more detections than mbx_coco_accumulate takes are accumulated by numpy."""
     packed = pack(gt_annotations, pred_annotations)
-    return accumulate(packed, *match_device(packed))
+    if not (np.isfinite(packed.dt).all() and np.isfinite(packed.gt).all()):
+        return accumulate(packed, *match_device(packed))                  # (warns; match_host inside)
+    m = match_device(packed, on_device=True)
+    try:
+        return _summarize(*accumulate_device(packed, *m))
+    except AccumulateUnsupported:
+        return accumulate(packed, *(t.cpu().numpy() if hasattr(t, "cpu") else t for t in m))

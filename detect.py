@@ -31,7 +31,9 @@ def parse_args():
     p.add_argument("--merge_per_image", action="store_true",
                    help="[new] also write results-merged-<global_step>.json: per image, the candidates of all its patches "
                         "ordered by score, de-duplicated by greedy NMS across patches (DETECTION.MERGE_IOU_THRESHOLD, "
-                        "default 0.5; null = none) and cut to --max_detections")
+                        "default 0.5; null = none) and cut to --max_detections; DETECTION.MERGE_VOTE_IOU_THRESHOLD "
+                        "(absent or null = off; in (0, 1]) replaces every kept box by the score-weighted mean of all the "
+                        "image's candidates that overlap it at least that much (box voting)")
     p.add_argument("--keep_partial_batch", action="store_true",
                    help="[new] also process the last incomplete batch (the reference's tf.train.batch drops it)")
     return p.parse_args()
@@ -54,6 +56,15 @@ def main():
     cfg = with_defaults(parse_config_file(args.config_file))
     if not args.tfrecords and not args.synthetic:
         raise SystemExit("give --tfrecords FILE... or --synthetic N")
+    # DETECTION.MERGE_VOTE_IOU_THRESHOLD (not a key of the reference; read with --merge_per_image only): box voting in the
+    # per-image merge.  Absent or null = off; checked here, before the GPU is touched
+    merge_vote_iou = None
+    if args.merge_per_image:
+        from multibox_amd import records as REC
+        try:
+            merge_vote_iou = REC.merge_vote_iou((cfg.get("DETECTION", None) or {}).get("MERGE_VOTE_IOU_THRESHOLD", None))
+        except ValueError as e:
+            raise SystemExit("DETECTION.MERGE_VOTE_IOU_THRESHOLD: %s" % e)
     torch.cuda.set_device(local_rank)
     if world > 1:       # results are gathered as host objects: gloo is enough, no GPU collective on this path
         torch.distributed.init_process_group("gloo")
@@ -170,7 +181,7 @@ def main():
         # DETECTION.MERGE_IOU_THRESHOLD (not a key of the reference): 0.5 when absent, null = no suppression (top-N per image)
         merge_iou = det.get("MERGE_IOU_THRESHOLD", 0.5)
         if rank == 0:
-            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou)
+            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou, vote_iou=merge_vote_iou)
 
     def merge_feed(hb, hs, hc, ids_, hw_last):
         merger.add(hb, hs, hc, ids_)

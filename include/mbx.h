@@ -140,6 +140,36 @@ int mbx_merge_detections(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const 
                          float* out_scores /*[I,max_det]*/, int32_t* out_src /*[I,max_det]*/,
                          int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/, mbx_stream_t stream);
 
+/* mbx_merge_detections with BOX VOTING (optional, off by default in detect.py): every kept box is replaced by the
+ * score-weighted mean of all candidates of its image that overlap it strongly.  The kept list, its order, out_scores,
+ * out_src, out_count and out_status are exactly what mbx_merge_detections writes for the same arguments (the same kernel
+ * runs first): iou_threshold = +infinity (plain top-N), the max_det cut and the status-1 refusal above
+ * MBX_MERGE_MAX_CANDIDATES included.  The candidates of image i are the slots [0, clamp(count[r], 0, k_max)) of its rows,
+ * as above -- EVERY one: suppressed ones, kept ones and the ones past the max_det cut; a slot at or past count[r] is
+ * never read.  Candidate c VOTES for kept box e iff its score is finite and > 0 (a NaN, +-0, a negative score and
+ * +infinity do not vote) and IoU(e, c) >= vote_iou_threshold, the IoU in float64 in the operation order of mbx_nms
+ * (iw = min(e.x2, c.x2) - max(e.x1, c.x1), ih alike; inter = iw > 0 && ih > 0 ? iw * ih : 0; uni = area(e) + area(c) -
+ * inter; uni > 0 ? inter / uni : 0), so membership is exact against a numpy restatement.  A kept box of positive width
+ * and height with a votable score votes for itself (IoU exactly 1); a kept box of area <= 0 has no voters.
+ *   out_votes[i,k]  the number n of voters; unused slots 0
+ *   out_boxes[i,k]  n == 0: the kept candidate's own bytes, as in the plain merge; otherwise coordinate j is
+ *                   (sum_c w_c * x_cj) / (sum_c w_c) in float64 with w_c = (double)score_c, every product rounded once
+ *                   (no fused multiply-add); unused slots 0
+ * The sums are taken in an order that is a function of the image's own rows only (per lane over the rows in order, then
+ * a fixed tree; no floating-point atomics): an image's outputs do not depend on I, on its place in the launch or on the
+ * other images, and the same input gives the same bits on every call.  Any order keeps
+ * |out - exact| <= (2n + 4) * 2^-53 * (sum w|x|) / (sum w) per coordinate.
+ * vote_iou_threshold outside (0, 1] or NaN, or a null out_votes: MBX_ERR_INVALID_ARG, nothing launched; every other check
+ * as mbx_merge_detections (max_det > 640: MBX_ERR_UNSUPPORTED; I == 0: MBX_OK, nothing launched).  Two launches on
+ * `stream`: the merge (one workgroup per image), then the vote (one wavefront per two kept boxes).
+ * Whether voting raises AP on real data is NOT measured here: no trained model or dataset is at hand.             */
+int mbx_merge_detections_voted(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const float* scores /*[R,k_max]*/,
+                               const int32_t* count /*[R]*/, const int32_t* image_rows /*[I+1] ascending*/, int I,
+                               int k_max, int max_det, double iou_threshold, double vote_iou_threshold,
+                               double* out_boxes /*[I,max_det,4]*/, float* out_scores /*[I,max_det]*/,
+                               int32_t* out_src /*[I,max_det]*/, int32_t* out_count /*[I]*/,
+                               int32_t* out_status /*[I]*/, int32_t* out_votes /*[I,max_det]*/, mbx_stream_t stream);
+
 /* ------------------------------------------------------ COCO metric: matching (eval.py:212-226)
  * Replaces the matching step of the metric eval.py:212-226 runs: pycocotools' COCOeval.evaluateImg (iouType 'bbox',
  * useCats = 0, no crowd annotations), once per image, area range and IoU threshold; multibox_amd/cocoeval.py:_evaluate_img

@@ -1,4 +1,4 @@
-// libmbx: per-image merge of multi-crop detections (greedy NMS across patches + top-N).
+// libmbx: per-image merge of multi-crop detections (greedy NMS across patches + top-N), and box voting on what it keeps.
 // The reference writes every patch's boxes one after the other (detect.py:408-460) and has no such stage; this one is
 // optional and sits behind mbx_decode_filter_topk (+ mbx_nms), reading exactly what they write.  Built with
 // -ffp-contract=off: the float64 IoU keeps the operation order of oracle.ref_numpy.nms_greedy, so keep decisions are exact.
@@ -192,6 +192,122 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------ box voting
+constexpr int kVotePerWave = 2;                        // kept boxes per wavefront: every candidate load serves both
+constexpr int kVotePerBlock = kWaves * kVotePerWave;
+
+// IoU of the kept box e and the candidate b of area ab: the terms of suppresses() above, which stays the code it was
+__device__ __forceinline__ double vote_iou(const Box& e, const Box& b, double ab) {
+  const double iw = fmin(e.x2, b.x2) - fmax(e.x1, b.x1), ih = fmin(e.y2, b.y2) - fmax(e.y1, b.y1);
+  const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
+  const double uni = (e.x2 - e.x1) * (e.y2 - e.y1) + ab - inter;
+  return uni > 0.0 ? inter / uni : 0.0;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One candidate (score w, box b) against the wavefront's kept boxes: the sums of those it votes for.
+__device__ __forceinline__ void vote_add(float w, const Box& b, const Box (&e)[kVotePerWave], double vthr,
+                                         double (&sw)[kVotePerWave], double (&sx)[kVotePerWave][4], int (&nv)[kVotePerWave]) {
+  if (!(w > 0.f && w < INFINITY)) return;                            // NaN, +-0, negatives and +inf do not vote
+  const double ab = (b.x2 - b.x1) * (b.y2 - b.y1), wd = (double)w;
+#pragma unroll
+  for (int j = 0; j < kVotePerWave; ++j) {
+    if (vote_iou(e[j], b, ab) >= vthr) {
+      sw[j] += wd;
+      sx[j][0] += wd * b.x1; sx[j][1] += wd * b.y1; sx[j][2] += wd * b.x2; sx[j][3] += wd * b.y2;
+      ++nv[j];
+    }
+  }
+}
+
+// Second launch behind merge_kernel, grid (groups of kVotePerBlock kept slots, images): one wavefront per kVotePerWave
+// kept boxes of one image.  It reads the kept boxes merge_kernel wrote to out_boxes and ALL candidates of the image
+// (slots [0, count[r]) of its rows), keeps per kept box sum(w), sum(w * x_j) and the number of voters in registers, and
+// ends with the fixed xor tree of wave_sum_f64.  The rows are taken kVoteRows at a time: lane l first takes slot l of
+// each of them (their loads are issued together: a row of the usual 50 candidates is one pass, and one load's latency
+// per row was most of the kernel's time), then slots l + 64, l + 128, ... of each.  So the order of the sums depends
+// on the image's own rows only.  Each wavefront writes the slots it read and no other.
+constexpr int kVoteRows = 4;
+static_assert(64 % kVoteRows == 0, "a group of rows does not wrap around the 64 counts a wavefront holds");
+
+__global__ void __launch_bounds__(kThreads)
+vote_kernel(const double* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ count,
+            const int32_t* __restrict__ image_rows, int img0, int k_max, int max_det, double vthr,
+            double* out_boxes, const int32_t* __restrict__ out_count, int32_t* __restrict__ out_votes) {
+  const int img = img0 + blockIdx.y, lane = threadIdx.x & 63;
+  const int k0 = (blockIdx.x * kWaves + (threadIdx.x >> 6)) * kVotePerWave;
+  if (k0 >= max_det) return;
+  const int nk = min(max(out_count[img], 0), max_det);
+  double* ob = out_boxes + (size_t)img * max_det * 4;
+  int32_t* ov = out_votes + (size_t)img * max_det;
+  if (k0 >= nk) {                                                    // unused slots: boxes are merge_kernel's zeros
+    if (lane < kVotePerWave && k0 + lane < max_det) ov[k0 + lane] = 0;
+    return;
+  }
+  Box e[kVotePerWave];
+  double sw[kVotePerWave], sx[kVotePerWave][4];
+  int nv[kVotePerWave];
+#pragma unroll
+  for (int q = 0; q < kVotePerWave; ++q) {
+    const int k = min(k0 + q, nk - 1);                               // (a slot past nk repeats the last box; not written)
+    e[q].x1 = ob[k * 4]; e[q].y1 = ob[k * 4 + 1]; e[q].x2 = ob[k * 4 + 2]; e[q].y2 = ob[k * 4 + 3];
+    sw[q] = sx[q][0] = sx[q][1] = sx[q][2] = sx[q][3] = 0.0;
+    nv[q] = 0;
+  }
+  const int r0 = image_rows[img], r1 = image_rows[img + 1];
+  for (int t0 = r0; t0 < r1; t0 += 64) {
+    const int nrows = min(64, r1 - t0);
+    const int my_cnt = lane < nrows ? min(max(count[t0 + lane], 0), k_max) : 0;      // 64 rows' counts, one load
+    for (int q = 0; q < nrows; q += kVoteRows) {
+      int c[kVoteRows];
+      float w[kVoteRows];
+      Box b[kVoteRows];
+#pragma unroll
+      for (int u = 0; u < kVoteRows; ++u) {                          // slot `lane` of kVoteRows rows (rows past nrows: count 0)
+        c[u] = __shfl(my_cnt, (q + u) & 63, 64);
+        w[u] = 0.f;
+        b[u].x1 = b[u].y1 = b[u].x2 = b[u].y2 = 0.0;
+        if (lane < c[u]) {
+          const size_t at = (size_t)(t0 + q + u) * k_max + lane;
+          w[u] = scores[at];
+          b[u].x1 = boxes[at * 4]; b[u].y1 = boxes[at * 4 + 1]; b[u].x2 = boxes[at * 4 + 2]; b[u].y2 = boxes[at * 4 + 3];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kVoteRows; ++u) vote_add(w[u], b[u], e, vthr, sw, sx, nv);      // (w = 0 where there is no slot)
+#pragma unroll
+      for (int u = 0; u < kVoteRows; ++u) {                          // what a row has beyond 64 candidates
+        for (int s = lane + 64; s < c[u]; s += 64) {
+          const size_t at = (size_t)(t0 + q + u) * k_max + s;
+          Box bb;
+          bb.x1 = boxes[at * 4]; bb.y1 = boxes[at * 4 + 1]; bb.x2 = boxes[at * 4 + 2]; bb.y2 = boxes[at * 4 + 3];
+          vote_add(scores[at], bb, e, vthr, sw, sx, nv);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kVotePerWave; ++q) {
+    int n = nv[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    const double w = wave_sum_f64(sw[q]);
+    const double x1 = wave_sum_f64(sx[q][0]), y1 = wave_sum_f64(sx[q][1]);
+    const double x2 = wave_sum_f64(sx[q][2]), y2 = wave_sum_f64(sx[q][3]);
+    const int k = k0 + q;
+    if (lane == 0 && k < max_det) {
+      const bool used = k < nk;
+      ov[k] = used ? n : 0;
+      if (used && n > 0) { ob[k * 4] = x1 / w; ob[k * 4 + 1] = y1 / w; ob[k * 4 + 2] = x2 / w; ob[k * 4 + 3] = y2 / w; }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int mbx_merge_detections(const double* boxes, const float* scores, const int32_t* count,
@@ -212,5 +328,28 @@ extern "C" int mbx_merge_detections(const double* boxes, const float* scores, co
   hipLaunchKernelGGL(merge_kernel, dim3(I), dim3(kThreads), lds, mbx_s(stream), boxes, scores, count, image_rows, k_max,
                      max_det, iou_threshold, use_iou, out_boxes, out_scores, out_src, out_count, out_status);
   MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" int mbx_merge_detections_voted(const double* boxes, const float* scores, const int32_t* count,
+                                          const int32_t* image_rows, int I, int k_max, int max_det, double iou_threshold,
+                                          double vote_iou_threshold, double* out_boxes, float* out_scores,
+                                          int32_t* out_src, int32_t* out_count, int32_t* out_status, int32_t* out_votes,
+                                          mbx_stream_t stream) {
+  if (!out_votes) return MBX_ERR_INVALID_ARG;
+  if (!(vote_iou_threshold > 0.0 && vote_iou_threshold <= 1.0)) return MBX_ERR_INVALID_ARG;       // a NaN too
+  // the kept list: the plain merge itself, its argument checks included
+  const int rc = mbx_merge_detections(boxes, scores, count, image_rows, I, k_max, max_det, iou_threshold, out_boxes,
+                                      out_scores, out_src, out_count, out_status, stream);
+  if (rc != MBX_OK || I == 0) return rc;
+  MBX_ENTER();
+  const int groups = (max_det + kVotePerBlock - 1) / kVotePerBlock;
+  for (int i0 = 0; i0 < I;) {
+    const int ni = I - i0 < 65535 ? I - i0 : 65535;                     // (the y extent of a grid)
+    hipLaunchKernelGGL(vote_kernel, dim3(groups, ni), dim3(kThreads), 0, mbx_s(stream), boxes, scores, count, image_rows,
+                       i0, k_max, max_det, vote_iou_threshold, out_boxes, out_count, out_votes);
+    MBX_LAUNCH_CHECK();
+    i0 += ni;
+  }
   return MBX_OK;
 }

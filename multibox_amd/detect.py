@@ -111,11 +111,16 @@ class ImageMerger:
     """All candidates of one image, from all its patches, ordered by score, de-duplicated by greedy NMS across patches and
     cut to max_detections (mbx_merge_detections, one workgroup per image).  Fed with the HOST copies of the per-patch
     stage's output, batch by batch in stream order -- the same path for one rank and for many; the rows of one image
-    are adjacent, an image may straddle batches.  iou_threshold None or inf: no suppression, top-N per image."""
+    are adjacent, an image may straddle batches.  iou_threshold None or inf: no suppression, top-N per image.
+    vote_iou None: the kept boxes are the kept candidates' own (mbx_merge_detections, as ever).  A float in (0, 1]: box
+    voting (mbx_merge_detections_voted) -- the same kept list and scores, every kept box replaced by the score-weighted
+    mean of all candidates of its image with IoU >= vote_iou against it.  An image above 16 384 candidates is still cut
+    to its best 16 384 on the host first, and only those vote."""
 
-    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256):
+    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256, vote_iou=None):
         self.K, self.max_det = int(k_max), int(max_detections)
         self.thr = float("inf") if iou_threshold is None else float(iou_threshold)
+        self.vote_iou = REC.merge_vote_iou(vote_iou)
         self.device, self.flush_images = device, max(1, int(flush_images))
         self.stream = torch.cuda.Stream(device=device)      # its uploads and launches do not queue behind the detect loop
         self._rows, self._ids, self._runs = [], [], 0
@@ -172,11 +177,20 @@ class ImageMerger:
             o_src = torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
             o_count = torch.empty((n_img,), dtype=torch.int32, device=self.device)
             o_status = torch.empty((n_img,), dtype=torch.int32, device=self.device)
-            _lib.check(_lib.lib().mbx_merge_detections(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
-                                                       d_rows.data_ptr(), n_img, self.K, self.max_det, self.thr,
-                                                       o_boxes.data_ptr(), o_scores.data_ptr(), o_src.data_ptr(),
-                                                       o_count.data_ptr(), o_status.data_ptr(), self.stream.cuda_stream),
-                       "mbx_merge_detections")
+            if self.vote_iou is None:
+                _lib.check(_lib.lib().mbx_merge_detections(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
+                                                           d_rows.data_ptr(), n_img, self.K, self.max_det, self.thr,
+                                                           o_boxes.data_ptr(), o_scores.data_ptr(), o_src.data_ptr(),
+                                                           o_count.data_ptr(), o_status.data_ptr(), self.stream.cuda_stream),
+                           "mbx_merge_detections")
+            else:
+                o_votes = torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
+                _lib.check(_lib.lib().mbx_merge_detections_voted(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
+                                                                 d_rows.data_ptr(), n_img, self.K, self.max_det, self.thr,
+                                                                 self.vote_iou, o_boxes.data_ptr(), o_scores.data_ptr(),
+                                                                 o_src.data_ptr(), o_count.data_ptr(), o_status.data_ptr(),
+                                                                 o_votes.data_ptr(), self.stream.cuda_stream),
+                           "mbx_merge_detections_voted")
             status = o_status.cpu().numpy()
             if status.any():
                 raise _lib.MbxError("mbx_merge_detections: status %d for image %r" % (int(status.max()), ids[int(np.argmax(status != 0))]))

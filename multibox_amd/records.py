@@ -34,6 +34,20 @@ def batch_chunk(boxes, scores, count, image_ids):
 MERGE_MAX_CANDIDATES = 16384           # MBX_MERGE_MAX_CANDIDATES (include/mbx.h)
 
 
+def merge_vote_iou(value):
+    """DETECTION.MERGE_VOTE_IOU_THRESHOLD / ImageMerger(vote_iou=): None = no box voting, else a float in (0, 1] (the
+    range mbx_merge_detections_voted accepts); anything else is a ValueError."""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (0.0 < v <= 1.0):
+        raise ValueError("the vote IoU threshold must be a number in (0, 1] or null (no box voting), not %r" % (value,))
+    return v
+
+
 def group_rows(image_ids):
     """Runs of equal consecutive ids in stream order: (ids, image_rows [len(ids) + 1] int32); image i owns the rows
     [image_rows[i], image_rows[i + 1]).  An id that returns later is a new image; the padding rows of a partial batch

@@ -1,7 +1,10 @@
 """mbx_merge_detections timing on seeded candidates (multibox_amd.synth.merge_candidates): device events around 20 launches
 after 3 warm-ups, for (a) 256 images of the config.yaml.example VGA plan (44 rows per image: 1 x 200 + 43 x 50 candidates,
 k_max 200, max_det 100, IoU 0.5) and (b) 64 images x 80 rows x 200 candidates (max_det 300, IoU 0.3).
-usage: python tools/merge_bench.py"""
+--vote_iou X also times mbx_merge_detections_voted (box voting at vote IoU X: the merge launch + the vote launch) on the
+same inputs: five rounds of 20 plain and 20 voted launches in turn, the median round of each.
+usage: python tools/merge_bench.py [--vote_iou X]"""
+import argparse
 import hashlib
 import os
 import sys
@@ -11,6 +14,9 @@ import numpy as np
 import torch
 import __graft_entry__ as g
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--vote_iou", type=float, default=None)
+args = ap.parse_args()
 g.build()
 from multibox_amd import _lib
 from multibox_amd.synth import merge_candidates
@@ -31,18 +37,41 @@ for name, I, rows, K, n_obj, max_det, thr in (("a: VGA plan", 256, 44, 200, 8, 1
     call = lambda: _lib.check(l.mbx_merge_detections(d_b.data_ptr(), d_s.data_ptr(), d_c.data_ptr(), d_r.data_ptr(), I, K, max_det,
                                                      thr, o_b.data_ptr(), o_s.data_ptr(), o_i.data_ptr(), o_c.data_ptr(),
                                                      o_st.data_ptr(), s), "mbx_merge_detections")
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(20):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / 20 * 1e3
     for _ in range(3):
         call()
     torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(20):
-        call()
-    b.record()
-    torch.cuda.synchronize()
-    us = a.elapsed_time(b) / 20 * 1e3
+    us = timed(call)
     sha = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in (o_b, o_s, o_i, o_c, o_st))).hexdigest()[:12]
     n_cand = int(count.sum())
     print("%s: I=%d rows=%d k_max=%d max_det=%d iou=%.1f: %.1f us/launch  %.0f images/s  %.3g candidates/s  kept %d..%d  "
           "status_max %d  outputs sha %s" % (name, I, rows, K, max_det, thr, us, I / us * 1e6, n_cand / us * 1e6, int(o_c.min()),
                                              int(o_c.max()), int(o_st.max()), sha), flush=True)
+    if args.vote_iou is None:
+        continue
+    o_v = torch.empty((I, max_det), dtype=torch.int32, device="cuda")
+    voted = lambda: _lib.check(l.mbx_merge_detections_voted(d_b.data_ptr(), d_s.data_ptr(), d_c.data_ptr(), d_r.data_ptr(), I, K,
+                                                            max_det, thr, args.vote_iou, o_b.data_ptr(), o_s.data_ptr(),
+                                                            o_i.data_ptr(), o_c.data_ptr(), o_st.data_ptr(), o_v.data_ptr(), s),
+                               "mbx_merge_detections_voted")
+    for _ in range(3):
+        voted()
+    torch.cuda.synchronize()
+    t_plain, t_voted = [], []
+    for _ in range(5):
+        t_plain.append(timed(call))
+        t_voted.append(timed(voted))
+    sha_v = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in (o_b, o_s, o_i, o_c, o_st, o_v))).hexdigest()[:12]
+    votes = o_v.cpu().numpy()[np.arange(max_det)[None, :] < o_c.cpu().numpy()[:, None]]
+    fmt = lambda t: "%.1f us/launch (rounds %s)" % (float(np.median(t)), " ".join("%.1f" % v for v in t))
+    print("%s: vote_iou=%.2f: plain %s  voted %s  vote launch +%.1f us  votes per kept box min %d median %d max %d  "
+          "outputs sha %s" % (name[0], args.vote_iou, fmt(t_plain), fmt(t_voted), float(np.median(t_voted) - np.median(t_plain)),
+                              int(votes.min()), int(np.median(votes)), int(votes.max()), sha_v), flush=True)

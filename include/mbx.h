@@ -409,6 +409,15 @@ typedef struct {
   const mbx_bn_bwd_fused* bn_bwd;         /* HOST, may be NULL: see above (round 6) */
 } mbx_conv_desc;
 #define MBX_CONV_TILE_CONFIGS 14
+/* tile_config beyond the igemm3 tiles 1..MBX_CONV_TILE_CONFIGS: the launch families, described below */
+#define MBX_TILE_I5_BASE 32        /* + t + 1 (33..39): the persistent igemm5 launch, tile t */
+#define MBX_TILE_I7 65             /* the persistent pointwise launch, filter panel resident in LDS */
+#define MBX_TILE_DIRECT3 96        /* the direct 3x3 launch (and the network's first layer) */
+#define MBX_TILE_DIRECTW 97        /* the whole-width direct 3x3 launch */
+#define MBX_TILE_RESIDENT 98       /* the resident-image launch */
+#define MBX_TILE_PWRES 99          /* the pixel-resident pointwise launch */
+#define MBX_TILE_SPLITK_BASE 128   /* + S: split-K in S slices, 2 <= S <= MBX_TILE_SPLITK_MAX */
+#define MBX_TILE_SPLITK_MAX 32
 /* tile_config 33..39: the persistent igemm5 launch (128x64, 128x128, 192x128, 256x128, 256x64, 128x192, 128x256 tiles; 128x192
    without the accumulate + mask epilogue); 65: the persistent
    POINTWISE launch with the filter panel resident in LDS (1x1, unit stride, unpadded, 64 < K <= 384, no statistics; its

@@ -61,12 +61,6 @@ __device__ __forceinline__ uint64_t score_key(double s) {
   return ~asc;
 }
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __global__ void __launch_bounds__(256) acc_fill_kernel(double* __restrict__ precision, int np, double* __restrict__ recall, int nr) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < np) precision[e] = -1.0;

@@ -17,22 +17,6 @@
 
 #include "conv_common.h"
 
-// conv5.hip: persistent igemm5 launches (mbx_conv_desc.tile_config = kI5Flag + index + 1)
-int mbx_launch_igemm5(void* convk, int index, hipStream_t s);
-// conv7.hip: the panel-resident pointwise launch (mbx_conv_desc.tile_config = kI7Cfg)
-int mbx_launch_igemm7(void* convk, hipStream_t s);
-// convd.hip: the direct 3x3 launch for few channels on large maps (mbx_conv_desc.tile_config = kDirectCfg)
-int mbx_launch_direct3(void* convk, int N, int H_out, hipStream_t s);
-int mbx_direct3_grid(int N, int H_out, int W_out);
-int mbx_launch_directw(void* convk, int N, int H_out, hipStream_t s);
-int mbx_directw_grid(int N, int H_out, int W_out);
-// convr.hip: the resident-image launch for multi-tap convolutions on small maps (mbx_conv_desc.tile_config = kResidentCfg)
-int mbx_launch_resident(void* convk, int N, int H_out, hipStream_t s);
-int mbx_resident_rows(int N);
-int mbx_launch_pwres(void* convk, hipStream_t s);
-extern const int mbx_i5_tiles[][2];
-extern const int mbx_i5_num_tiles;
-
 namespace {
 
 // EV: epilogue variant fixed at compile time (no per-element branching):
@@ -1150,16 +1134,17 @@ int pick_cfg(long M, int C_out) {
 
 
 
-constexpr int kNumCfgs = 14;
+constexpr int kNumCfgs = MBX_CONV_TILE_CONFIGS;
 static_assert(kGbCtlWords * 4 == MBX_GRID_BARRIER_BYTES && kFbSlots == MBX_BN_BWD_SLOTS, "include/mbx.h and csrc/grid_barrier.h agree");
-constexpr int kI5Flag = 32;      // mbx_conv_desc.tile_config = 32 + t: igemm5 tile t (conv5.hip), persistent launch
-constexpr int kI7Cfg = 65;       // mbx_conv_desc.tile_config = 65: igemm7 (conv7.hip), persistent pointwise launch with the filter panel in LDS
-constexpr int kDirectCfg = 96;   // mbx_conv_desc.tile_config = 96: the direct 3x3 launch (convd.hip)
-constexpr int kDirectWCfg = 97;  // mbx_conv_desc.tile_config = 97: the whole-width direct 3x3 launch for narrow maps (convd.hip)
-constexpr int kPwResCfg = 99;    // mbx_conv_desc.tile_config = 99: the pixel-resident pointwise launch for the epilogue-bound 1x1 layers (convr.hip)
-constexpr int kResidentCfg = 98; // mbx_conv_desc.tile_config = 98: the resident-image launch for 1x7 / 7x1 layers on small maps (convr.hip)
-constexpr int kSplitFlag = 128;  // mbx_conv_desc.tile_config = 128 + S: split-K in S slices (float32 partials + reduce launch)
-constexpr int kSplitMax = 32;
+// mbx_conv_desc.tile_config beyond the igemm3 tiles 1..kNumCfgs: the launch families (include/mbx.h)
+constexpr int kI5Flag = MBX_TILE_I5_BASE;         // + t + 1: igemm5 tile t (conv5.hip), persistent launch
+constexpr int kI7Cfg = MBX_TILE_I7;               // igemm7 (conv7.hip), persistent pointwise launch with the filter panel in LDS
+constexpr int kDirectCfg = MBX_TILE_DIRECT3;      // the direct 3x3 launch (convd.hip)
+constexpr int kDirectWCfg = MBX_TILE_DIRECTW;     // the whole-width direct 3x3 launch for narrow maps (convd.hip)
+constexpr int kResidentCfg = MBX_TILE_RESIDENT;   // the resident-image launch for 1x7 / 7x1 layers on small maps (convr.hip)
+constexpr int kPwResCfg = MBX_TILE_PWRES;         // the pixel-resident pointwise launch for the epilogue-bound 1x1 layers (convr.hip)
+constexpr int kSplitFlag = MBX_TILE_SPLITK_BASE;  // + S: split-K in S slices (float32 partials + reduce launch)
+constexpr int kSplitMax = MBX_TILE_SPLITK_MAX;
 // slices really used and K steps per slice for a request of S slices over nk K steps (no empty slice)
 inline void splitk_geom(int nk, int S, int& ksplit, int& kps) {
   if (S > nk) S = nk;
@@ -1168,8 +1153,7 @@ inline void splitk_geom(int nk, int S, int& ksplit, int& kps) {
   ksplit = (nk + kps - 1) / kps;
 }
 int choose_cfg(long M, int C_out, int desc_cfg) {
-  static int force = -2;
-  if (force == -2) { const char* e = getenv("MBX_FORCE_CFG"); force = e ? atoi(e) : -1; }
+  static const int force = mbx_env_int("MBX_FORCE_CFG", -1);
   if (force >= 0) return force;
   if (desc_cfg > 0 && desc_cfg <= kNumCfgs) return desc_cfg - 1;       // the caller measured (mbx_conv_desc.tile_config)
   // measured on MI355X (tools/kbench.py, all B=64 layer shapes, plain / residual / accumulate epilogues): the
@@ -1414,12 +1398,10 @@ static int conv_impl(const mbx_conv_desc* d, mbx_stream_t stream, int dry) {
       k.fb.mean[i] = b->mean[i]; k.fb.rstd[i] = b->rstd[i]; k.fb.beta[i] = b->beta[i]; k.fb.dbeta[i] = b->dbeta[i];
       k.fb.acc[i] = b->acc[i]; k.fb.acc_ld[i] = b->acc_ld[i]; k.fb.relu[i] = b->relu[i];
     }
-    static int fault = -1;
-    if (fault < 0) { const char* e = getenv("MBX_DEBUG_BARRIER_FAULT"); fault = (e && e[0] == '3') ? 1 : 0; }   // '3': the fused BACKWARD barriers
+    const int fault = mbx_barrier_fault() == '3';             // '3': the fused BACKWARD barriers
     k.fb.n = b->n;
     k.fb.bar = reinterpret_cast<unsigned*>(b->barrier);
-    static int probe = -1;
-    if (probe < 0) { const char* e = getenv("MBX_FUSED_PROBE"); probe = e ? (atoi(e) & ~1) : 0; }
+    static const int probe = mbx_env_int("MBX_FUSED_PROBE", 0) & ~1;
     k.fb.spin_limit = fault ? (1u << 10) : (1u << 22); k.fb.fault = fault | probe; k.fb.step_poison = b->step_poison;
     k.fb.inv_M = (float)(1.0 / (double)Mll);
   }
@@ -1436,11 +1418,9 @@ static int conv_impl(const mbx_conv_desc* d, mbx_stream_t stream, int dry) {
       return MBX_ERR_UNSUPPORTED;
     const int tc = d->tile_config;
     if (!((tc > kI5Flag && tc <= kI5Flag + 7) || tc == kDirectWCfg || tc == kResidentCfg)) return MBX_ERR_UNSUPPORTED;
-    static int fault = -1;
-    if (fault < 0) { const char* e = getenv("MBX_DEBUG_BARRIER_FAULT"); fault = (e && e[0] == '2') ? 1 : 0; }   // '2': the FORWARD barriers
+    const int fault = mbx_barrier_fault() == '2';             // '2': the FORWARD barriers
     k.fa.bar = reinterpret_cast<unsigned*>(b->barrier);
-    static int probe = -1;                                  // MBX_FUSED_PROBE: timing probes of tools/fused_probe.py (WRONG results)
-    if (probe < 0) { const char* e = getenv("MBX_FUSED_PROBE"); probe = e ? (atoi(e) & ~1) : 0; }
+    static const int probe = mbx_env_int("MBX_FUSED_PROBE", 0) & ~1;      // timing probes of tools/fused_probe.py (WRONG results)
     k.fa.spin_limit = fault ? (1u << 10) : (1u << 22); k.fa.fault = fault | probe; k.fa.step_poison = b->step_poison;
     k.fa.a = reinterpret_cast<unsigned short*>(b->a); k.fa.ld_a = b->ld_a; k.fa.beta = b->beta;
     k.fa.mean = b->mean; k.fa.rstd = b->rstd; k.fa.mmean = b->moving_mean; k.fa.mvar = b->moving_var; k.fa.thr = b->relu_thr;
@@ -1491,13 +1471,12 @@ static int conv_impl(const mbx_conv_desc* d, mbx_stream_t stream, int dry) {
   {  // debug build (MBX_BUILD_DEFS=-DMBX_I5_STAMPS): MBX_I5_STAMP_PTR = device address of 64 x 8 x 4 uint64 (tools/i5_stamps.py)
     static const unsigned long long sp = getenv("MBX_I5_STAMP_PTR") ? strtoull(getenv("MBX_I5_STAMP_PTR"), nullptr, 10) : 0ull;
     k.stamps = reinterpret_cast<unsigned long long*>(sp);
-    k.dbg = getenv("MBX_I5_DBG") ? atoi(getenv("MBX_I5_DBG")) : 0;      // (read per call: tools switch it between launches)
-    k.stagger = getenv("MBX_STAGGER") ? atoi(getenv("MBX_STAGGER")) : 0;
+    k.dbg = mbx_env_int("MBX_I5_DBG", 0);                // (read per call: tools switch it between launches)
+    k.stagger = mbx_env_int("MBX_STAGGER", 0);
   }
 #endif
   for (int c = 0; c < 4; ++c) { k.cls_m0[c] = 0; k.cls_hw[c] = 1; k.cls_w[c] = 1; }
-  static int notap = -1;
-  if (notap < 0) { const char* e = getenv("MBX_NO_TAP_SKIP"); notap = (e && e[0] == '1') ? 1 : 0; }
+  static const bool notap = mbx_env_char("MBX_NO_TAP_SKIP") == '1';
   if (k.shift && d->C_in % 64 == 0 && !notap) {  // K tiles never straddle filter taps: whole taps can be skipped
     // parity classes of the output pixels (class = (oh & 1) * 2 + (ow & 1)); an empty class has the start of the
     // next one, so pixel_class() steps over it
@@ -1537,12 +1516,12 @@ static int conv_impl(const mbx_conv_desc* d, mbx_stream_t stream, int dry) {
     MBX_LAUNCH_CHECK();
     return MBX_OK;
   }
-  if (d->tile_config == kDirectCfg) return mbx_launch_direct3(&k, d->N, d->H_out, s);
-  if (d->tile_config == kDirectWCfg) return mbx_launch_directw(&k, d->N, d->H_out, s);
-  if (d->tile_config == kResidentCfg) return mbx_launch_resident(&k, d->N, d->H_out, s);
-  if (d->tile_config == kPwResCfg) return mbx_launch_pwres(&k, s);
-  if (d->tile_config == kI7Cfg) return mbx_launch_igemm7(&k, s);
-  if (d->tile_config > kI5Flag) return mbx_launch_igemm5(&k, d->tile_config - kI5Flag - 1, s);
+  if (d->tile_config == kDirectCfg) return mbx_launch_direct3(k, d->N, d->H_out, s);
+  if (d->tile_config == kDirectWCfg) return mbx_launch_directw(k, d->N, d->H_out, s);
+  if (d->tile_config == kResidentCfg) return mbx_launch_resident(k, d->N, d->H_out, s);
+  if (d->tile_config == kPwResCfg) return mbx_launch_pwres(k, s);
+  if (d->tile_config == kI7Cfg) return mbx_launch_igemm7(k, s);
+  if (d->tile_config > kI5Flag) return mbx_launch_igemm5(k, d->tile_config - kI5Flag - 1, s);
   switch (choose_cfg(k.M, k.C_out, d->tile_config)) {
     case 0: return launch_igemm<128, 128, 2, 2>(k, s);
     case 1: return launch_igemm<128, 64, 2, 2>(k, s);
@@ -1588,8 +1567,7 @@ static int fill_wgrad(const mbx_conv_desc* d, const void* dy, int64_t dy_img_str
   k2.pw = (d->R == 1 && d->S == 1 && d->pad_t == 0 && d->pad_l == 0 && d->stride == 1 &&
            d->x_img_stride == (int64_t)d->H_in * d->W_in * d->ldx) ? 1 : 0;
   k2.ydense = (dy_img_stride == (int64_t)k.HW_out * ld_dy) ? 1 : 0;
-  static int dbg = -1;
-  if (dbg < 0) { const char* e = getenv("MBX_WG_DBG"); dbg = e ? atoi(e) : 0; }
+  static const int dbg = mbx_env_int("MBX_WG_DBG", 0);
   k2.dbg = dbg;
   return MBX_OK;
 }
@@ -1606,12 +1584,7 @@ extern "C" int mbx_conv_wgrad_scaled(const mbx_conv_desc* d, const void* dy, int
   k.tiles_n = narrow ? (k.C_out + 63) / 64 : (k.C_out + 127) / 128;
   const int tiles = k.tiles_n * k.tiles_k;
   // split the pixel reduction so that ~2 blocks per CU exist, at least 256 pixels per split
-  static int env_ng = 0, env_target = 0;
-  if (!env_ng) {
-    const char* g1 = getenv("MBX_WGRAD_NG");
-    env_ng = (g1 && g1[0] == '1') ? 1 : 2;
-    const char* e = getenv("MBX_WGRAD_TARGET"); env_target = e ? atoi(e) : -1;
-  }
+  static const int env_ng = mbx_env_char("MBX_WGRAD_NG") == '1' ? 1 : 2, env_target = mbx_env_int("MBX_WGRAD_TARGET", -1);
   // mbx_conv_desc.tile_config selects the block shape for the weight gradient too: 0 library default (eight waves,
   // 256 blocks: one per CU), 1 eight waves / 256, 2 four waves / 512 (two per CU), 3 eight waves / 192, 4 four waves / 384,
   // 5 eight waves / 128, 6 eight waves / 224
@@ -1693,18 +1666,6 @@ extern "C" int mbx_conv_wgrad_scaled(const mbx_conv_desc* d, const void* dy, int
 
 // ------------------------------------------------------------------------------------ grouped weight gradient
 // Host-side plan: [WgradLayer x n_jobs | WgradItem x n_items] image that the caller copies to device memory once.
-static int plan_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n;
-    else
-      ncu = 256;                       // no device visible (planning on a CPU-only host): MI355X
-  }
-  return ncu;
-}
-
 struct PlanJob { int cfg, ny, nx, tiles_n, tiles_k, steps, splits; double step_cost; };
 struct PlanGroup { int job, m_begin, m_end, tiles; double len; };     // all output tiles of one (layer, pixel range)
 
@@ -1722,8 +1683,7 @@ static void plan_jobs(const mbx_wgrad_job* jobs, int n_jobs, int flags, std::vec
     const long long M = (long long)d.N * d.H_out * d.W_out;
     const int Ktot = d.R * d.S * d.C_in;
     double best = 1e300;
-    static int max_cfg = -1;
-    if (max_cfg < 0) { const char* e = getenv("MBX_WG_MAXCFG"); max_cfg = e ? atoi(e) : kNumWgCfgs; }   // bisecting aid
+    static const int max_cfg = mbx_env_int("MBX_WG_MAXCFG", kNumWgCfgs);       // bisecting aid
     for (int c = 0; c < kNumWgCfgs && c < max_cfg; ++c) {
       const int ny = kWgCfgs[c][0], nx = kWgCfgs[c][1];
       const int tn = (d.C_out + 64 * ny - 1) / (64 * ny), tk = (Ktot + 64 * nx - 1) / (64 * nx);
@@ -1735,7 +1695,7 @@ static void plan_jobs(const mbx_wgrad_job* jobs, int n_jobs, int flags, std::vec
     pj[j].steps = (int)((M + 63) / 64);
     total += (double)pj[j].tiles_n * pj[j].tiles_k * pj[j].steps * pj[j].step_cost;
   }
-  const double share = total / plan_cus();
+  const double share = total / conv_cus();
   static double wdiv = 0.0;
   if (wdiv == 0.0) { const char* e = getenv("MBX_WG_WMAX_DIV"); wdiv = e ? atof(e) : 4.0; if (wdiv <= 0.0) wdiv = 4.0; }   // (A/B knob)
   double wmax = share / wdiv;
@@ -1879,7 +1839,7 @@ extern "C" int mbx_conv_wgrad_grouped_capped(void* device_image, const mbx_wgrad
   char* base = reinterpret_cast<char*>(device_image);
   hipStream_t s = mbx_s(stream);
   // (queue heads: zero in the plan image, and reset by the kernel's last block at the end of every launch)
-  int blocks = info->n_items < plan_cus() ? info->n_items : plan_cus();            // one persistent block per CU
+  int blocks = info->n_items < conv_cus() ? info->n_items : conv_cus();            // one persistent block per CU
   if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;     // (the queues are drained by any number)
   hipLaunchKernelGGL(conv_wgrad_grouped_kernel, dim3(blocks), dim3(64 * (8 + kWgLoaders)), kLds, s,
                      reinterpret_cast<const WgradLayer*>(base + info->layers_off),

@@ -387,11 +387,7 @@ int launch5(ConvK& k, hipStream_t s) {
   k.tiles_n = (k.C_out + G::BN - 1) / G::BN;
   k.stats_cap = stats_cap_for(k.tiles_m);
   const int ntiles = k.tiles_m * k.tiles_n;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
+  const int ncu = conv_cus();
   int grid = ntiles < ncu ? ntiles : ncu;                           // one persistent block per CU
   if (k.max_wg > 0 && grid > k.max_wg) grid = k.max_wg;             // ... or fewer: CUs left to a kernel on another stream
   const int ev = k.epi == MBX_EPI_RESIDUAL ? 4 : k.epi == MBX_EPI_AFFINE ? 3 : k.bw_n ? 6 : k.stats ? 1 : k.bits ? 7 : (k.accumulate || k.skip) ? 2 : 0;
@@ -436,12 +432,11 @@ int launch5(ConvK& k, hipStream_t s) {
 
 }  // namespace
 
-// tile shapes of the igemm5 launch: mbx_conv_desc.tile_config = 32 + index + 1
+// tile shapes of the igemm5 launch: mbx_conv_desc.tile_config = MBX_TILE_I5_BASE + index + 1
 extern const int mbx_i5_tiles[][2] = {{128, 64}, {128, 128}, {192, 128}, {256, 128}, {256, 64}, {128, 192}, {128, 256}};
 extern const int mbx_i5_num_tiles = 7;
 
-int mbx_launch_igemm5(void* convk, int index, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_igemm5(ConvK& k, int index, hipStream_t s) {
   if (k.shift || k.epi == MBX_EPI_STORE_F32) return MBX_ERR_UNSUPPORTED;   // stride-2 data gradient / float32 heads: igemm3
   switch (index) {
     case 0: return launch5<2, 1>(k, s);

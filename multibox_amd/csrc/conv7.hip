@@ -206,19 +206,14 @@ conv_igemm7_kernel(const ConvK p) {
 
 }  // namespace
 
-// mbx_conv_desc.tile_config = 65: the panel-resident pointwise launch.  Returns MBX_ERR_UNSUPPORTED for anything but a
+// mbx_conv_desc.tile_config = MBX_TILE_I7: the panel-resident pointwise launch.  Returns MBX_ERR_UNSUPPORTED for anything but a
 // pointwise convolution with 64 < K <= 384 and a bf16 store / accumulate / affine / residual epilogue without statistics.
-int mbx_launch_igemm7(void* convk, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_igemm7(ConvK& k, hipStream_t s) {
   const int nk = (k.Ktot + 63) >> 6;
   if (!k.pw || k.shift || k.stats || k.bw_n || k.epi == MBX_EPI_STORE_F32 || nk < 2 || nk > k7MaxNk || (k.C_in % 8)) return MBX_ERR_UNSUPPORTED;
   k.tiles_m = (k.M + k7BM - 1) / k7BM;
   k.tiles_n = (k.C_out + k7BN - 1) / k7BN;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
+  const int ncu = conv_cus();
   const long ntiles = (long)k.tiles_m * k.tiles_n;
   int grid = ntiles < ncu ? (int)ntiles : ncu;                      // one persistent workgroup per CU, dealt round-robin to the column tiles
   if (k.max_wg > 0 && grid > k.max_wg) grid = k.max_wg;             // (mbx_conv_desc.max_workgroups)

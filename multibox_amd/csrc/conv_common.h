@@ -1,48 +1,15 @@
-// Device helpers and the kernel parameter block shared by the convolution translation units (conv.hip: igemm3 +
-// weight gradients + host entry points; conv5.hip: the persistent igemm5 kernel).  gfx950 only.
+// The kernel parameter block, the launch interface and the device helpers shared by the convolution translation units:
+// conv.hip (igemm3, weight gradients, the C entry points and conv_impl, the dispatcher) and one file per launch family --
+// conv5.hip (persistent igemm5), conv7.hip (panel-resident pointwise igemm7), convd.hip (direct 3x3 / whole-width / stem),
+// convr.hip (resident-image and pixel-resident pointwise).  gfx950 only.
 #pragma once
 #include "common.h"
 #include "grid_barrier.h"
 
-namespace {
-
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vector: stays in registers
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-// Two floats to one packed bf16 pair (lo in bits 0..15) in ONE v_cvt_pk_bf16_f32: the same rounding as f2bf, which the
-// compiler emits as one conversion PER VALUE plus a shift and an or (4 instructions a pair instead of 1).
-__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
-  typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(pk_f32x2{lo, hi}, pk_bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-// Lanes l, l + 16, l + 32, l + 48 (the four rows of a wave) each hold one byte (bits 0..7 of b, the rest zero): all four
-// get the dword [row 0 | row 1 << 8 | row 2 << 16 | row 3 << 24].  EXEC must be all ones.
-__device__ __forceinline__ unsigned gather4_rows(unsigned b) {
-  typedef unsigned g4_u32x2 __attribute__((ext_vector_type(2)));
-  const g4_u32x2 r = __builtin_amdgcn_permlane16_swap(b, b, false, false);     // (even row, odd row) of the lane's row pair
-  const unsigned t = r.x | (r.y << 8);
-  const g4_u32x2 q = __builtin_amdgcn_permlane32_swap(t, t, false, false);     // (lower half, upper half)
-  return q.x | (q.y << 16);
-}
-// max(x, 0) in one v_max_f32 (fmaxf costs a second one: the compiler canonicalises its operand first).  Inline asm is
-// invisible to the compiler's hazard checks: apply it ONLY to the result of a VALU instruction, never straight to an MFMA
-// accumulator (the affine / residual arithmetic always comes first).  The packed conversion above is the vector form of
-// the plain cast for the same reason: it IS the first reader of the accumulators in the store epilogues.
-__device__ __forceinline__ float relu_f(float x) {
-  float r;
-  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
+// ConvK is ONE type in every translation unit (a named namespace: the family launchers below take it by reference and the
+// linker checks their signatures); the kernels and device helpers stay file-local.  Every file of the library is compiled
+// with the same MBX_BUILD_DEFS, so the debug members at its end are in all of them or in none.
+namespace mbx {
 
 struct ConvK {
   const unsigned short* x; int x_img_stride, ldx, H_in, W_in, C_in;
@@ -94,7 +61,70 @@ struct ConvK {
 #endif
 };
 
+}  // namespace mbx
+
+// The launch families conv_impl dispatches to by mbx_conv_desc.tile_config (MBX_TILE_*, include/mbx.h).  Each fills in its
+// tile geometry, checks that the family applies (MBX_ERR_UNSUPPORTED otherwise) and launches unless k.dry is set.
+int mbx_launch_igemm5(mbx::ConvK& k, int index, hipStream_t s);              // conv5.hip: MBX_TILE_I5_BASE + index + 1
+extern const int mbx_i5_tiles[][2];                                          //   its tile shapes {BM, BN}
+extern const int mbx_i5_num_tiles;
+int mbx_launch_igemm7(mbx::ConvK& k, hipStream_t s);                         // conv7.hip: MBX_TILE_I7
+int mbx_launch_direct3(mbx::ConvK& k, int N, int H_out, hipStream_t s);      // convd.hip: MBX_TILE_DIRECT3
+int mbx_direct3_grid(int N, int H_out, int W_out);                           //   workgroups = statistics rows
+int mbx_launch_directw(mbx::ConvK& k, int N, int H_out, hipStream_t s);      // convd.hip: MBX_TILE_DIRECTW
+int mbx_directw_grid(int N, int H_out, int W_out);
+int mbx_launch_resident(mbx::ConvK& k, int N, int H_out, hipStream_t s);     // convr.hip: MBX_TILE_RESIDENT
+int mbx_resident_rows(int N);                                                //   statistics rows (one per image)
+int mbx_launch_pwres(mbx::ConvK& k, hipStream_t s);                          // convr.hip: MBX_TILE_PWRES
+
+namespace {
+
+using mbx::ConvK;
+using mbx::FusedApply;
+using mbx::FusedBwd;
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;   // native vector: stays in registers
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+
+__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
+__device__ __forceinline__ unsigned short f2bf(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+// Two floats to one packed bf16 pair (lo in bits 0..15) in ONE v_cvt_pk_bf16_f32: the same rounding as f2bf, which the
+// compiler emits as one conversion PER VALUE plus a shift and an or (4 instructions a pair instead of 1).
+__device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
+  typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(pk_f32x2{lo, hi}, pk_bf16x2));
+}
+__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+// Lanes l, l + 16, l + 32, l + 48 (the four rows of a wave) each hold one byte (bits 0..7 of b, the rest zero): all four
+// get the dword [row 0 | row 1 << 8 | row 2 << 16 | row 3 << 24].  EXEC must be all ones.
+__device__ __forceinline__ unsigned gather4_rows(unsigned b) {
+  typedef unsigned g4_u32x2 __attribute__((ext_vector_type(2)));
+  const g4_u32x2 r = __builtin_amdgcn_permlane16_swap(b, b, false, false);     // (even row, odd row) of the lane's row pair
+  const unsigned t = r.x | (r.y << 8);
+  const g4_u32x2 q = __builtin_amdgcn_permlane32_swap(t, t, false, false);     // (lower half, upper half)
+  return q.x | (q.y << 16);
+}
+// max(x, 0) in one v_max_f32 (fmaxf costs a second one: the compiler canonicalises its operand first).  Inline asm is
+// invisible to the compiler's hazard checks: apply it ONLY to the result of a VALU instruction, never straight to an MFMA
+// accumulator (the affine / residual arithmetic always comes first).  The packed conversion above is the vector form of
+// the plain cast for the same reason: it IS the first reader of the accumulators in the store epilogues.
+__device__ __forceinline__ float relu_f(float x) {
+  float r;
+  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
 constexpr int kThreads = 256;
+
+// CUs the persistent launches size their grids by (and the grouped weight gradient plans for); no device visible -- planning
+// or mbx_conv_supported on a CPU-only host: MI355X
+inline int conv_cus() { const int n = mbx_cu_count(); return n ? n : 256; }
 
 // sum over the 16 lanes of a DPP row (lanes sharing lane >> 4): four v_add_f32_dpp row_ror, every lane ends up with the
 // row sum -- no LDS traffic (ds_bpermute shuffles made the epilogue VALU/LDS-bound).  Written as ONE asm block of fused

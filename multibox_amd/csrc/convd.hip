@@ -860,37 +860,27 @@ int launch_direct3(const ConvK& k, const DirK& q, int grid, hipStream_t s) {
   return MBX_OK;
 }
 
-int direct3_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  return ncu;
-}
-
 }  // namespace
 
 // workgroups (= statistics rows) of the direct launch for an N x H_out x W_out output
 int mbx_direct3_grid(int N, int H_out, int W_out) {
   const long nt = (long)N * ((H_out + kDTH - 1) / kDTH) * ((W_out + kDTW - 1) / kDTW);
-  const int ncu = direct3_cus();
+  const int ncu = conv_cus();
   return nt < ncu ? (int)nt : ncu;
 }
 
-// workgroups (= statistics rows) of the whole-width direct launch (tile_config 97)
+// workgroups (= statistics rows) of the whole-width direct launch (MBX_TILE_DIRECTW)
 int mbx_directw_grid(int N, int H_out, int W_out) {
   const int th = directw_th(W_out);
   if (!th) return 0;
   const long nt = (long)N * ((H_out + th - 1) / th);
-  const int ncu = direct3_cus();
+  const int ncu = conv_cus();
   return nt < ncu ? (int)nt : ncu;
 }
 
-// mbx_conv_desc.tile_config = 97: the whole-width direct 3x3 launch (conv_directw_kernel) -- 3x3 / stride 1, forward or data
+// mbx_conv_desc.tile_config = MBX_TILE_DIRECTW: the whole-width direct 3x3 launch (conv_directw_kernel) -- 3x3 / stride 1, forward or data
 // gradient, C_in 32 / 48 / 64, C_out <= 64 (a multiple of 8), maps 8..64 wide; bf16 store with or without statistics, or affine.
-int mbx_launch_directw(void* convk, int N, int H_out, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_directw(ConvK& k, int N, int H_out, hipStream_t s) {
   if (k.R != 3 || k.S != 3 || k.mul != 1 || k.shift || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits ||
       k.rscale != 0.f || k.bw_n || (k.epi == MBX_EPI_AFFINE && k.stats))
     return MBX_ERR_UNSUPPORTED;
@@ -915,11 +905,10 @@ int mbx_launch_directw(void* convk, int N, int H_out, hipStream_t s) {
   return MBX_ERR_UNSUPPORTED;                             // 64 -> 64: filter image + two patches do not fit 160 KB of LDS
 }
 
-// mbx_conv_desc.tile_config = 96: the direct 3x3 launch.  MBX_ERR_UNSUPPORTED for anything but a 3x3 / stride-1 convolution
+// mbx_conv_desc.tile_config = MBX_TILE_DIRECT3: the direct 3x3 launch.  MBX_ERR_UNSUPPORTED for anything but a 3x3 / stride-1 convolution
 // (forward, or the data gradient of one) with C_in in {32, 64}, C_out <= 64 (a multiple of 8) and a bf16 store epilogue
 // with or without statistics, or the affine (+ relu) epilogue of a folded batch norm.
-int mbx_launch_direct3(void* convk, int N, int H_out, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_direct3(ConvK& k, int N, int H_out, hipStream_t s) {
   if (k.mul == 2 && !k.shift && k.C_in == 8) {
     // the network's first layer (forward only: stride 2, packed RGB input): conv_stem_kernel
     if (k.R != 3 || k.S != 3 || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits || k.rscale != 0.f || k.bw_n ||

@@ -736,8 +736,6 @@ conv_pwres_kernel(const ConvK p, const PwK q) {
 #undef MBXP_STAMP
 }
 
-int resident_cus();
-
 template <int C8, int MIH, int EV>
 int launch_pwres(const ConvK& k, PwK& q, hipStream_t s) {
   using G = PwG<C8, MIH>;
@@ -745,7 +743,7 @@ int launch_pwres(const ConvK& k, PwK& q, hipStream_t s) {
   static_assert(lds <= 160 * 1024, "LDS");
   q.npt = (k.M + G::PIX - 1) / G::PIX;
   q.nct = (k.C_out + kPwCol - 1) / kPwCol;
-  const int ncu = resident_cus();
+  const int ncu = conv_cus();
   int ncs = ncu / q.npt;                                  // column splits: as many units as fit one round of workgroups
   if (ncs < 1) ncs = 1;
   if (ncs > q.nct) ncs = q.nct;
@@ -764,15 +762,6 @@ int launch_pwres(const ConvK& k, PwK& q, hipStream_t s) {
   hipLaunchKernelGGL((conv_pwres_kernel<C8, MIH, EV>), dim3(grid), dim3(kRThreads), lds, s, k, q);
   MBX_LAUNCH_CHECK();
   return MBX_OK;
-}
-
-int resident_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  return ncu;
 }
 
 template <int C8, int NB, int RS, int MI, int HWC>
@@ -810,12 +799,11 @@ inline void resident_groups(int C_out, int& NG, int& CPT, int& NB) {
 // statistics rows of the resident-image launch (a row per image)
 int mbx_resident_rows(int N) { return N; }
 
-// mbx_conv_desc.tile_config = 98: the RESIDENT-IMAGE launch (conv_resident_kernel).  MBX_ERR_UNSUPPORTED for anything but a
+// mbx_conv_desc.tile_config = MBX_TILE_RESIDENT: the RESIDENT-IMAGE launch (conv_resident_kernel).  MBX_ERR_UNSUPPORTED for anything but a
 // stride-1 convolution with "same" geometry (forward, or the data gradient of one) of 7 taps on a map of 65 .. 289 pixels
 // (17 x 17) with C_in 128 / 160 / 192, or of 3 taps on an 8 x 8 map with C_in 192 / 224 / 256; C_out a multiple of 8 and a bf16 store epilogue with or without statistics, or
 // the affine (+ relu) epilogue of a folded batch norm.
-int mbx_launch_resident(void* convk, int N, int H_out, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_resident(ConvK& k, int N, int H_out, hipStream_t s) {
   if (k.mul != 1 || k.shift || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits || k.rscale != 0.f ||
       k.bw_n || (k.epi == MBX_EPI_AFFINE && k.stats))
     return MBX_ERR_UNSUPPORTED;
@@ -833,7 +821,7 @@ int mbx_launch_resident(void* convk, int N, int H_out, hipStream_t s) {
   if (RS > 9) return MBX_ERR_UNSUPPORTED;
   for (int t = 0; t < 9; ++t) { q.dh[t] = q.dw[t] = q.dd[t] = 0; }
   for (int t = 0; t < RS; ++t) { q.dh[t] = t / k.S - k.pad_t; q.dw[t] = t % k.S - k.pad_l; q.dd[t] = q.dh[t] * q.W + q.dw[t]; }
-  int grid = q.ntiles < resident_cus() ? q.ntiles : resident_cus();
+  int grid = q.ntiles < conv_cus() ? q.ntiles : conv_cus();
   if (k.max_wg > 0 && grid > k.max_wg) grid = k.max_wg;
   // consecutive tiles per workgroup (BATCH_SIZE 256: the four channel groups of an image -- its image lands once, and the next
   // group's filter slice while this one's outputs are stored)
@@ -854,11 +842,10 @@ int mbx_launch_resident(void* convk, int N, int H_out, hipStream_t s) {
   return MBX_ERR_UNSUPPORTED;
 }
 
-// mbx_conv_desc.tile_config = 99: the PIXEL-RESIDENT pointwise launch (conv_pwres_kernel).  MBX_ERR_UNSUPPORTED for anything but
+// mbx_conv_desc.tile_config = MBX_TILE_PWRES: the PIXEL-RESIDENT pointwise launch (conv_pwres_kernel).  MBX_ERR_UNSUPPORTED for anything but
 // a 1x1 / stride-1 / unpadded convolution with C_in 96 / 128 / 320 / 384 / 448 and a residual epilogue (+ relu, + sign bits) or a
 // bf16 store masked by relu sign bits (with or without an accumulate source).
-int mbx_launch_pwres(void* convk, hipStream_t s) {
-  ConvK& k = *reinterpret_cast<ConvK*>(convk);
+int mbx_launch_pwres(ConvK& k, hipStream_t s) {
   if (!k.pw || k.shift || k.stats || k.bw_n || k.C_out % 8) return MBX_ERR_UNSUPPORTED;
   const bool res = k.epi == MBX_EPI_RESIDUAL, accm = k.epi == MBX_EPI_STORE && k.bits && !k.skip;     // (masks by the sign bits only)
   if (!res && !accm) return MBX_ERR_UNSUPPORTED;

@@ -15,6 +15,9 @@
 
 namespace {
 
+using mbx::FusedApply;
+using mbx::FusedBwd;
+
 // 16-byte load that is COHERENT AT DEVICE SCOPE (sc1: served at the memory side like the atomics that produced the data) but an
 // ordinary load to the compiler: a run of them is issued back to back and waited for once.  (`__hip_atomic_load` compiles to
 // the same instruction, but as an atomic it is never batched: a rolled loop of them waited for every single round trip --

@@ -22,6 +22,7 @@
 #endif
 constexpr int kGbSub = 16, kGbRel = 32, kGbLine = 32;            // arrival counters / release words / 4-byte words per line
 constexpr int kGbCtlWords = kGbLine * (2 + kGbSub + kGbRel);     // line 0: {grid size, timeout flag}; 6.4 KB per barrier
+constexpr int kFbSlots = 8;                // FusedBwd: accumulator copies (a workgroup adds into copy blockIdx % kFbSlots)
 
 __device__ __forceinline__ unsigned gb_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ long long gb_ld(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -56,6 +57,9 @@ __device__ __forceinline__ bool grid_barrier_arrive_wait(unsigned* ctl, const un
   return timed_out;
 }
 
+// (the two structs below are embedded in mbx::ConvK by value: named namespace, one type in every translation unit)
+namespace mbx {
+
 // The batch-norm APPLY of the layer a training-mode convolution just wrote, run as the tail of that launch (fused_bn.h).
 struct FusedApply {
   unsigned* bar;                 // grid-barrier control block (kGbCtlWords, ZERO at launch); NULL: not fused
@@ -67,11 +71,9 @@ struct FusedApply {
   int relu; float eps, decay; double inv_count;
 };
 
-
 // The batch-norm BACKWARD of the layers whose activation gradient a data-gradient launch writes, run as the tail of that launch
 // (fused_bn.h).  Output channels [cb[i], cb[i + 1]) of the launch belong to segment i: a batch-norm layer (or a channel range of
 // one) with its pre-BN output y, its gradient dy, statistics and accumulators, all pointers AT THE SEGMENT'S FIRST CHANNEL.
-constexpr int kFbSlots = 8;                // accumulator copies (a workgroup adds into copy blockIdx % kFbSlots)
 struct FusedBwd {
   unsigned* bar;                           // grid-barrier control block (ZERO at launch); NULL: not fused
   unsigned spin_limit; int fault;
@@ -86,3 +88,5 @@ struct FusedBwd {
   int relu[4];
   float inv_M;
 };
+
+}  // namespace mbx

@@ -2,8 +2,7 @@
 // The reference writes every patch's boxes one after the other (detect.py:408-460) and has no such stage; this one is
 // optional and sits behind mbx_decode_filter_topk (+ mbx_nms), reading exactly what they write.  Built with
 // -ffp-contract=off: the float64 IoU keeps the operation order of oracle.ref_numpy.nms_greedy, so keep decisions are exact.
-#include "common.h"
-#include <math.h>
+#include "boxes.h"
 
 namespace {
 
@@ -14,15 +13,9 @@ constexpr int kMaxCand = MBX_MERGE_MAX_CANDIDATES;
 // chunk of kThreads candidates [kThreads][4] f64.  640 is what fits beside the keys in the 160 KiB of a workgroup.
 constexpr int kMergeMaxDet = 640;
 
-struct Box { double x1, y1, x2, y2; };
-
-// does the EARLIER (kept) box e suppress the later box b of area ab?  oracle.ref_numpy.nms_greedy, term by term
+// does the EARLIER (kept) box e suppress the later box b of area ab?  oracle.ref_numpy.nms_greedy (boxes.h)
 __device__ __forceinline__ bool suppresses(const Box& e, const Box& b, double ab, double thr) {
-  const double iw = fmin(e.x2, b.x2) - fmax(e.x1, b.x1), ih = fmin(e.y2, b.y2) - fmax(e.y1, b.y1);
-  const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
-  const double uni = (e.x2 - e.x1) * (e.y2 - e.y1) + ab - inter;
-  const double iou = uni > 0.0 ? inter / uni : 0.0;
-  return iou > thr;
+  return iou_corners(e, b, ab) > thr;
 }
 
 __device__ __forceinline__ Box box_shfl(const Box& b, int src) {
@@ -66,8 +59,7 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
   // ---- 1a. number of candidates
   int mine = 0;
   for (int r = r0 + tid; r < r1; r += kThreads) mine += min(max(count[r], 0), k_max);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  mine = wave_sum(mine);
   if (lane == 0) wave_tot[tid >> 6] = mine;
   if (tid == 0) sh_nk = 0;
   __syncthreads();
@@ -92,28 +84,14 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
         const float* sr = scores + (size_t)(t0 + q) * k_max;
         const unsigned rel0 = (unsigned)(t0 + q - r0) * (unsigned)k_max;
         for (int s = tid; s < c; s += kThreads) {
-          const float v = sr[s];
-          unsigned u = __float_as_uint(v);
-          u = (v != v) ? 0xffffffffu : (v == 0.f) ? 0x80000000u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));   // -0 == +0
-          keys[off + s] = ((unsigned long long)u << 32) | (unsigned long long)(~(rel0 + (unsigned)s));
+          keys[off + s] = ((unsigned long long)score_order_key(sr[s]) << 32) | (unsigned long long)(~(rel0 + (unsigned)s));
         }
         off += c;
       }
     }
     for (int j = total + tid; j < N; j += kThreads) keys[j] = 0ull;      // below every candidate's key (its score image is > 0)
     __syncthreads();
-    for (int size = 2; size <= N; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < (N >> 1); t += kThreads) {
-          const int lo = 2 * t - (t & (stride - 1));
-          const int hi = lo + stride;
-          const bool desc = (lo & size) == 0;
-          const unsigned long long a = keys[lo], bb = keys[hi];
-          if ((a < bb) == desc) { keys[lo] = bb; keys[hi] = a; }
-        }
-        __syncthreads();
-      }
-    }
+    lds_bitonic_sort_desc(keys, N, tid, kThreads);
 
     if (!use_iou) {
       // ---- 2'. no suppression: the first max_det of the sorted list
@@ -136,7 +114,7 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
           const unsigned rel = ~(unsigned)(keys[c] & 0xffffffffull);
           const double* p = boxes + (size_t)(base + rel) * 4;
           b.x1 = p[0]; b.y1 = p[1]; b.x2 = p[2]; b.y2 = p[3];
-          const double ab = (b.x2 - b.x1) * (b.y2 - b.y1);
+          const double ab = box_area(b);
           for (int j = 0; j < nk && !dead; ++j) dead = suppresses(kept[j], b, ab, thr);
         }
         chunk[tid] = b;
@@ -150,7 +128,7 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
             unsigned long long alive = alive_mask[s];
             if (alive == 0ull) continue;
             const Box m = chunk[s * 64 + lane];
-            const double am = (m.x2 - m.x1) * (m.y2 - m.y1);
+            const double am = box_area(m);
             bool d = !((alive >> lane) & 1ull);
             for (int j = nk0; j < n && !d; ++j) d = suppresses(kept[j], m, am, thr);     // kept since this chunk began
             alive = __ballot(!d);
@@ -196,28 +174,14 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
 constexpr int kVotePerWave = 2;                        // kept boxes per wavefront: every candidate load serves both
 constexpr int kVotePerBlock = kWaves * kVotePerWave;
 
-// IoU of the kept box e and the candidate b of area ab: the terms of suppresses() above, which stays the code it was
-__device__ __forceinline__ double vote_iou(const Box& e, const Box& b, double ab) {
-  const double iw = fmin(e.x2, b.x2) - fmax(e.x1, b.x1), ih = fmin(e.y2, b.y2) - fmax(e.y1, b.y1);
-  const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
-  const double uni = (e.x2 - e.x1) * (e.y2 - e.y1) + ab - inter;
-  return uni > 0.0 ? inter / uni : 0.0;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One candidate (score w, box b) against the wavefront's kept boxes: the sums of those it votes for.
 __device__ __forceinline__ void vote_add(float w, const Box& b, const Box (&e)[kVotePerWave], double vthr,
                                          double (&sw)[kVotePerWave], double (&sx)[kVotePerWave][4], int (&nv)[kVotePerWave]) {
   if (!(w > 0.f && w < INFINITY)) return;                            // NaN, +-0, negatives and +inf do not vote
-  const double ab = (b.x2 - b.x1) * (b.y2 - b.y1), wd = (double)w;
+  const double ab = box_area(b), wd = (double)w;
 #pragma unroll
   for (int j = 0; j < kVotePerWave; ++j) {
-    if (vote_iou(e[j], b, ab) >= vthr) {
+    if (iou_corners(e[j], b, ab) >= vthr) {
       sw[j] += wd;
       sx[j][0] += wd * b.x1; sx[j][1] += wd * b.y1; sx[j][2] += wd * b.x2; sx[j][3] += wd * b.y2;
       ++nv[j];
@@ -228,7 +192,7 @@ __device__ __forceinline__ void vote_add(float w, const Box& b, const Box (&e)[k
 // Second launch behind merge_kernel, grid (groups of kVotePerBlock kept slots, images): one wavefront per kVotePerWave
 // kept boxes of one image.  It reads the kept boxes merge_kernel wrote to out_boxes and ALL candidates of the image
 // (slots [0, count[r]) of its rows), keeps per kept box sum(w), sum(w * x_j) and the number of voters in registers, and
-// ends with the fixed xor tree of wave_sum_f64.  The rows are taken kVoteRows at a time: lane l first takes slot l of
+// ends with the fixed xor tree of wave_sum.  The rows are taken kVoteRows at a time: lane l first takes slot l of
 // each of them (their loads are issued together: a row of the usual 50 candidates is one pass, and one load's latency
 // per row was most of the kernel's time), then slots l + 64, l + 128, ... of each.  So the order of the sums depends
 // on the image's own rows only.  Each wavefront writes the slots it read and no other.
@@ -293,12 +257,10 @@ vote_kernel(const double* __restrict__ boxes, const float* __restrict__ scores, 
   }
 #pragma unroll
   for (int q = 0; q < kVotePerWave; ++q) {
-    int n = nv[q];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    const double w = wave_sum_f64(sw[q]);
-    const double x1 = wave_sum_f64(sx[q][0]), y1 = wave_sum_f64(sx[q][1]);
-    const double x2 = wave_sum_f64(sx[q][2]), y2 = wave_sum_f64(sx[q][3]);
+    const int n = wave_sum(nv[q]);
+    const double w = wave_sum(sw[q]);
+    const double x1 = wave_sum(sx[q][0]), y1 = wave_sum(sx[q][1]);
+    const double x2 = wave_sum(sx[q][2]), y2 = wave_sum(sx[q][3]);
     const int k = k0 + q;
     if (lane == 0 && k < max_det) {
       const bool used = k < nk;

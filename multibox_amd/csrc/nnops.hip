@@ -18,7 +18,7 @@ __device__ __forceinline__ int xcd_logical(int bid, int nblk) {
   const int xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
-inline int xcd_rows_on() { static const int v = [] { const char* e = getenv("MBX_XCD_ROWS"); return e ? atoi(e) : 0; }(); return v; }
+inline int xcd_rows_on() { static const int v = mbx_env_int("MBX_XCD_ROWS", 0); return v; }
 
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -199,7 +199,7 @@ bn_apply_kernel(const unsigned short* __restrict__ y, long long M, int C, const 
 
 // ---------------------------------------------------------------- batch norm: backward
 struct BnBwdGeom { int C8, rows_per_iter, rpb, rows; };
-inline int bn_bwd_rows_target() { const char* e = getenv("MBX_BN_BWD_ROWS"); const int v = e ? atoi(e) : 2048; return v >= 64 && v <= 8192 ? v : 2048; }
+inline int bn_bwd_rows_target() { const int v = mbx_env_int("MBX_BN_BWD_ROWS", 2048); return v >= 64 && v <= 8192 ? v : 2048; }
 inline BnBwdGeom bn_bwd_geom(long long M, int C) {
   BnBwdGeom g;
   g.C8 = C / 8;
@@ -634,11 +634,10 @@ bn_bwd_rows_kernel(const float* __restrict__ part, int rows, double inv_M, const
   }
 }
 
-inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 inline void bn_fused_grid(long long M, int C, int rows, int& groups, int& chunks, int& rpc) {
   groups = (C + kBnGroup - 1) / kBnGroup;
   // every workgroup re-reduces rows x 64 partials: with many partial rows, fewer (longer) workgroups
-  static const int blocks_few = env_int("MBX_BN_FUSED_BLOCKS", 1024), blocks_many = env_int("MBX_BN_FUSED_BLOCKS_MANY", 256);
+  static const int blocks_few = mbx_env_int("MBX_BN_FUSED_BLOCKS", 1024), blocks_many = mbx_env_int("MBX_BN_FUSED_BLOCKS_MANY", 256);
   long long want = (rows > 16 ? blocks_many : blocks_few) / groups;
   if (want < 1) want = 1;
   long long maxc = (M + 255) / 256;
@@ -1852,18 +1851,6 @@ extern "C" int mbx_bn_bwd_apply_mapped(const void* da, int ld_da, const void* a,
   return MBX_OK;
 }
 
-static int ob_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      return 0;
-    ncu = n;
-  }
-  return ncu;
-}
-
 extern "C" int mbx_bn_bwd_apply_rows(const float* stats, int rows, const void* da, int ld_da, const void* y, int64_t M, int C,
                                      const float* mean, const float* rstd, const float* relu_thr, float* dbeta, void* dy,
                                      const mbx_chan_map* da_map, mbx_stream_t stream) {
@@ -1874,7 +1861,7 @@ extern "C" int mbx_bn_bwd_apply_rows(const float* stats, int rows, const void* d
   ChanMap cm;
   if (to_chan_map(da_map, C, cm) != MBX_OK) return MBX_ERR_INVALID_ARG;
   MBX_ENTER();
-  static const int rows_blocks = env_int("MBX_BN_ROWS_BLOCKS", 1024);
+  static const int rows_blocks = mbx_env_int("MBX_BN_ROWS_BLOCKS", 1024);
   const int C8 = C / 8, rpi = kT / C8 > 0 ? kT / C8 : 1;
   long long g = (M + rpi - 1) / rpi;
   if (g > rows_blocks) g = rows_blocks;
@@ -1890,7 +1877,7 @@ extern "C" size_t mbx_bn_bwd_onepass_workspace_bytes(int C) {
 
 // workgroups the grid may use: all CUs, or fewer when the caller keeps some free for a concurrent stream
 static int ob_groups(int max_workgroups) {
-  const int ncu = ob_cus();
+  const int ncu = mbx_cu_count();               // (0: no device -- the callers refuse)
   return (max_workgroups > 0 && max_workgroups < ncu) ? max_workgroups : ncu;
 }
 
@@ -1924,8 +1911,7 @@ extern "C" int mbx_bn_bwd_onepass_mapped(const void* da, int ld_da, int relu, co
   if (g.nv > kObMaxNV) return MBX_ERR_UNSUPPORTED;
   MBX_ENTER();
   const size_t lds = ((size_t)g.rpi * 2 * C + (size_t)(2 * C > kObT ? 2 * C : kObT)) * sizeof(float);   // rows + row parts
-  static int fault = -1;
-  if (fault < 0) { const char* e = getenv("MBX_DEBUG_BARRIER_FAULT"); fault = (e && e[0] == '1') ? 1 : 0; }
+  const int fault = mbx_barrier_fault() == '1';
   const unsigned spin_limit = fault ? (1u << 10) : (1u << 22);
 #define MBX_OB(NV, RELU)                                                                                               \
   hipLaunchKernelGGL((bn_bwd_onepass_kernel<NV, RELU>), dim3(g.G), dim3(kObT), lds, mbx_s(stream), (cus)da, ld_da,      \
@@ -2222,7 +2208,7 @@ extern "C" int mbx_bn_apply_fused_mapped(const void* stats_partial, int rows, in
   ChanMap cm;
   if (to_chan_map(a_map, C, cm) != MBX_OK) return MBX_ERR_INVALID_ARG;
   MBX_ENTER();
-  static const int rows_blocks = env_int("MBX_BN_ROWS_BLOCKS", 1024);
+  static const int rows_blocks = mbx_env_int("MBX_BN_ROWS_BLOCKS", 1024);
   // whole-row sweeps; every workgroup reduces the few fixed-point rows of all C channels itself (bn_apply_rows_kernel)
   const int C8 = C / 8, rpi = kT / C8 > 0 ? kT / C8 : 1;
   long long g = (M + rpi - 1) / rpi;
@@ -2244,8 +2230,8 @@ extern "C" int mbx_bn_apply_fused(const float* stats_partial, int rows, int64_t 
   // isolation (tools/bnf_bench.py) the fused launch wins up to ~1000 rows on small tensors (8 vs 13 us); inside the
   // captured step it LOSES 0.28 ms (round 2, same-box A/B, MBX_BN_FUSED_ROWS=1024): a graph-internal kernel boundary
   // costs ~1.5 us, the 5 us finalize overlaps the conv's tail, and 256 long workgroups stream a cold tensor badly.
-  static const int fused_rows = env_int("MBX_BN_FUSED_ROWS", 16);
-  static const long long fused_elems = env_int("MBX_BN_FUSED_KELEMS", 6200) * 1000LL;
+  static const int fused_rows = mbx_env_int("MBX_BN_FUSED_ROWS", 16);
+  static const long long fused_elems = mbx_env_int("MBX_BN_FUSED_KELEMS", 6200) * 1000LL;
   if (rows > 16 && (rows > fused_rows || M * C > fused_elems)) {
     int st = mbx_bn_finalize(stats_partial, rows, C, count, eps, decay, mean, rstd, mmean, mvar, stream);
     if (st != MBX_OK) return st;

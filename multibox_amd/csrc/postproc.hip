@@ -2,8 +2,7 @@
 // HBM/latency-bound integer+float kernels; one workgroup per image/patch,
 // wave64 shuffle reductions.  Built with -ffp-contract=off: the float32 cost arithmetic
 // must keep the reference's rounding sequence (loss.py:21-35).
-#include "common.h"
-#include <math.h>
+#include "boxes.h"
 
 namespace {
 
@@ -257,9 +256,9 @@ __global__ void loss_final_kernel(const double* __restrict__ partial, int B, flo
 
 // ------------------------------------------------------- decode + filter + top-K
 // Key: kept flag (bit 63) | order-preserving image of the confidence's float bits (32 bits) | prediction index
-// (31 bits); bitonic sort, descending.  The float image (flip the sign bit of non-negative values, all bits of
-// negative ones) orders ANY float like a comparison sort does -- negative scores and scores >= 2 included; a NaN
-// sorts above everything, where numpy's argsort(...)[::-1] (detect.py:423) puts it.
+// (31 bits); bitonic sort, descending.  The float image (score_order_key, boxes.h) orders ANY float like a comparison
+// sort does -- negative scores and scores >= 2 included; a NaN sorts above everything, where numpy's
+// argsort(...)[::-1] (detect.py:423) puts it.
 __global__ void __launch_bounds__(kThreads)
 decode_filter_topk_kernel(const float4* __restrict__ raw, const float* __restrict__ conf,
                           const float4* __restrict__ priors, const mbx_patch_meta* __restrict__ meta,
@@ -283,33 +282,19 @@ decode_filter_topk_kernel(const float4* __restrict__ raw, const float* __restric
       // detect.py:92-99 (strict)
       const bool drop = (x1 < m.restrictions[0]) || (y1 < m.restrictions[1]) || (x2 > m.restrictions[2]) || (y2 > m.restrictions[3]);
       if (!drop) {
-        const float cj = c[j];
-        unsigned u = __float_as_uint(cj);
-        u = (cj != cj) ? 0xffffffffu : (cj == 0.f) ? 0x80000000u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));   // -0 == +0
-        key = (1ull << 63) | ((unsigned long long)u << 31) | (unsigned long long)j;
+        key = (1ull << 63) | ((unsigned long long)score_order_key(c[j]) << 31) | (unsigned long long)j;
         ++kept;
       }
     }
     keys[j] = key;
   }
-  kept = (int)wave_sum((float)kept);
+  kept = wave_sum(kept);
   if ((tid & 63) == 0) kept_waves[tid >> 6] = kept;
   __syncthreads();
   int total_kept = 0;
   for (int w = 0; w < kWaves; ++w) total_kept += kept_waves[w];
 
-  for (int size = 2; size <= N; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (N >> 1); t += kThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long a = keys[lo], bb = keys[hi];
-        if ((a < bb) == desc) { keys[lo] = bb; keys[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort_desc(keys, N, tid, kThreads);
   int count = total_kept < m.max_to_keep ? total_kept : m.max_to_keep;   // detect.py:424
   if (count > k_max) count = k_max;
   if (count < 0) count = 0;
@@ -369,7 +354,7 @@ extern "C" int mbx_match(const float* decoded, const float* conf, const float* g
   if (B == 0) return MBX_OK;
   const size_t lds = match_lds_bytes(P, G);
   if (lds > 150 * 1024) return MBX_ERR_UNSUPPORTED;        // P > ~4200 at G=100
-  static const int force_nt = getenv("MBX_MATCH_THREADS") ? atoi(getenv("MBX_MATCH_THREADS")) : 0;      // (tools/match_bench.py)
+  static const int force_nt = mbx_env_int("MBX_MATCH_THREADS", 0);     // (tools/match_bench.py)
   const int nthreads = force_nt ? force_nt : (P > 1536 ? 512 : kThreads);
   MBX_ENTER();
   if (lds > 64 * 1024) {
@@ -428,17 +413,13 @@ nms_kernel(double* __restrict__ boxes, float* __restrict__ scores, int32_t* __re
   // pair (i, j), j > i: thread t takes row i = t / W', word w: 64 columns at a time
   for (int t = threadIdx.x; t < K * W; t += kThreads) {
     const int i = t / W, w = t - i * W;
-    const double x1 = bx[i * 4], y1 = bx[i * 4 + 1], x2 = bx[i * 4 + 2], y2 = bx[i * 4 + 3];
-    const double ai = (x2 - x1) * (y2 - y1);
+    const Box bi = {bx[i * 4], bx[i * 4 + 1], bx[i * 4 + 2], bx[i * 4 + 3]};
+    const double ai = box_area(bi);
     unsigned long long bits = 0ull;
     const int j0 = max(w * 64, i + 1), j1 = min(w * 64 + 64, K);
     for (int j = j0; j < j1; ++j) {
-      const double u1 = bx[j * 4], v1 = bx[j * 4 + 1], u2 = bx[j * 4 + 2], v2 = bx[j * 4 + 3];
-      const double iw = fmin(x2, u2) - fmax(x1, u1), ih = fmin(y2, v2) - fmax(y1, v1);
-      const double inter = (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
-      const double uni = ai + (u2 - u1) * (v2 - v1) - inter;
-      const double iou = uni > 0.0 ? inter / uni : 0.0;
-      if (iou > thr) bits |= 1ull << (j & 63);
+      const Box bj = {bx[j * 4], bx[j * 4 + 1], bx[j * 4 + 2], bx[j * 4 + 3]};
+      if (iou_corners(bi, bj, ai, box_area(bj)) > thr) bits |= 1ull << (j & 63);
     }
     rows[t] = bits;
   }

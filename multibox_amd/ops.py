@@ -202,6 +202,7 @@ def wgrad_overlap_cus():
     return max(0, int(os.environ.get("MBX_WG_OVERLAP", WG_OVERLAP_DEFAULT)))
 
 
+# mbx_conv_desc.tile_config: mirrors of MBX_CONV_TILE_CONFIGS / MBX_TILE_* (include/mbx.h; tests/test_cabi_cpu.py compares them)
 N_TILE_CONFIGS = 14
 I5_FLAG = 32                                   # tile_config 32 + t: persistent igemm5 launch (csrc/conv5.hip), tile t
 I5_TILE_CONFIGS = (33, 34, 35, 36, 37, 38, 39)     # 128x64, 128x128, 192x128, 256x128, 256x64, 128x192, 128x256

@@ -149,7 +149,8 @@ def test_ctypes_structs_match_the_header(tmp_path):
     """The ctypes mirrors of the C-ABI structs (ops.ConvDesc, ops.WgradJob, _lib.BnBwdStats) against include/mbx.h as a C
     compiler lays it out: size and the offset of every field of mbx_conv_desc (gcc on a ten-line program; no GPU).  A field
     added to the header and not to the mirror (or the other way round) shifts everything behind it -- mbx_wgrad_job embeds
-    the descriptor, so the library would read the job array with the wrong stride."""
+    the descriptor, so the library would read the job array with the wrong stride.  The same program prints the launch-family
+    values of tile_config (MBX_TILE_*), which ops.py mirrors as numbers."""
     import ctypes as C
     import shutil
     import subprocess
@@ -164,6 +165,13 @@ def test_ctypes_structs_match_the_header(tmp_path):
            '  printf("sizeof_bw %zu\\n", sizeof(mbx_bn_bwd_stats));',
            '  printf("sizeof_ba %zu\\n", sizeof(mbx_bn_apply_desc));', '  printf("sizeof_fb %zu\\n", sizeof(mbx_bn_bwd_fused));',
            '  printf("barrier_bytes %d\\n", MBX_GRID_BARRIER_BYTES);', '  printf("bwd_slots %d\\n", MBX_BN_BWD_SLOTS);']
+    # the launch-family values of mbx_conv_desc.tile_config: macro -> its mirror in ops.py
+    families = {"MBX_CONV_TILE_CONFIGS": ops.N_TILE_CONFIGS, "MBX_TILE_I5_BASE": ops.I5_FLAG, "MBX_TILE_I7": ops.I7_TILE_CONFIG,
+                "MBX_TILE_DIRECT3": ops.DIRECT3_TILE_CONFIG, "MBX_TILE_DIRECTW": ops.DIRECTW_TILE_CONFIG,
+                "MBX_TILE_RESIDENT": ops.RESIDENT_TILE_CONFIG, "MBX_TILE_PWRES": ops.PWRES_TILE_CONFIG,
+                "MBX_TILE_SPLITK_BASE": ops.SPLITK_FLAG, "MBX_TILE_SPLITK_MAX": None}
+    for m in families:
+        src.append('  printf("%s %%d\\n", %s);' % (m, m))
     for f in fields:
         src.append('  printf("%s %%zu\\n", offsetof(mbx_conv_desc, %s));' % (f, hdr.get(f, f)))
     # (round 6) the tables of the fused launches: every field of both
@@ -183,6 +191,16 @@ def test_ctypes_structs_match_the_header(tmp_path):
     assert int(out["sizeof_bw"]) == C.sizeof(_lib.BnBwdStats)
     assert int(out["sizeof_ba"]) == C.sizeof(ops.BnApplyDesc) and int(out["sizeof_fb"]) == C.sizeof(ops.BnBwdFused)
     assert int(out["barrier_bytes"]) == ops.GRID_BARRIER_BYTES and int(out["bwd_slots"]) == ops.BN_BWD_SLOTS
+    for m, mirror in families.items():
+        if mirror is not None:
+            assert int(out[m]) == mirror, m
+    assert 16 <= int(out["MBX_TILE_SPLITK_MAX"]) < int(out["MBX_TILE_SPLITK_BASE"])     # ops.splitk_slices asks for 2..16
+    # the persistent tiles: ops.I5_TILES against the library's own table (csrc/conv5.hip), their tile_config values in a row
+    l = _lib.lib()
+    n5 = C.c_int.in_dll(l, "mbx_i5_num_tiles").value
+    assert tuple(tuple(t) for t in ((C.c_int * 2) * n5).in_dll(l, "mbx_i5_tiles")) == ops.I5_TILES and n5 == len(ops.I5_TILES)
+    assert ops.I5_TILE_CONFIGS == tuple(ops.I5_FLAG + 1 + t for t in range(n5))
+    assert ops.I5_TILE_CONFIGS[-1] < ops.I7_TILE_CONFIG
     for f in fields:
         assert int(out[f]) == getattr(ops.ConvDesc, f).offset, f
     for f, _ in ops.BnApplyDesc._fields_:

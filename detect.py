@@ -33,7 +33,11 @@ def parse_args():
                         "ordered by score, de-duplicated by greedy NMS across patches (DETECTION.MERGE_IOU_THRESHOLD, "
                         "default 0.5; null = none) and cut to --max_detections; DETECTION.MERGE_VOTE_IOU_THRESHOLD "
                         "(absent or null = off; in (0, 1]) replaces every kept box by the score-weighted mean of all the "
-                        "image's candidates that overlap it at least that much (box voting)")
+                        "image's candidates that overlap it at least that much (box voting); DETECTION.MERGE_SOFT_NMS "
+                        "(absent or null = off; linear or gaussian) replaces the greedy NMS by Soft-NMS: an overlapping "
+                        "candidate's score is lowered (linear: by 1 - IoU above MERGE_IOU_THRESHOLD; gaussian: by "
+                        "exp(-IoU^2 / MERGE_SOFT_NMS_SIGMA), default 0.5) instead of the candidate deleted, candidates at or "
+                        "below MERGE_SOFT_NMS_MIN_SCORE (default 0.001) are dropped, and the file carries the decayed scores")
     p.add_argument("--keep_partial_batch", action="store_true",
                    help="[new] also process the last incomplete batch (the reference's tf.train.batch drops it)")
     return p.parse_args()
@@ -65,6 +69,30 @@ def main():
             merge_vote_iou = REC.merge_vote_iou((cfg.get("DETECTION", None) or {}).get("MERGE_VOTE_IOU_THRESHOLD", None))
         except ValueError as e:
             raise SystemExit("DETECTION.MERGE_VOTE_IOU_THRESHOLD: %s" % e)
+    # DETECTION.MERGE_SOFT_NMS (absent or null = off, linear, gaussian), MERGE_SOFT_NMS_SIGMA (0.5) and
+    # MERGE_SOFT_NMS_MIN_SCORE (0.001): Soft-NMS in the per-image merge, read and checked like the vote key.  Linear decays
+    # above DETECTION.MERGE_IOU_THRESHOLD (0.5 when absent; null is an error), gaussian does not read that key
+    merge_soft = None
+    if args.merge_per_image:
+        det_keys = cfg.get("DETECTION", None) or {}
+        try:
+            merge_soft = REC.merge_soft_nms(det_keys.get("MERGE_SOFT_NMS", None), det_keys.get("MERGE_SOFT_NMS_SIGMA", 0.5),
+                                            det_keys.get("MERGE_SOFT_NMS_MIN_SCORE", 0.001))
+        except ValueError as e:
+            raise SystemExit("DETECTION.MERGE_SOFT_NMS / MERGE_SOFT_NMS_SIGMA / MERGE_SOFT_NMS_MIN_SCORE: %s" % e)
+        if merge_soft is not None:
+            thr = det_keys.get("MERGE_IOU_THRESHOLD", 0.5)
+            if merge_soft[0] == REC.SOFT_NMS_METHODS["linear"]:
+                try:
+                    bad = thr is None or isinstance(thr, bool) or float(thr) != float(thr)
+                except (TypeError, ValueError):
+                    bad = True
+                if bad:
+                    raise SystemExit("DETECTION.MERGE_IOU_THRESHOLD: linear Soft-NMS (DETECTION.MERGE_SOFT_NMS) decays the scores "
+                                     "of candidates that overlap a picked box by more than this IoU; it must be a number, not %r" % (thr,))
+            elif "MERGE_IOU_THRESHOLD" in det_keys and rank == 0:
+                print("DETECTION.MERGE_IOU_THRESHOLD is ignored: gaussian Soft-NMS (DETECTION.MERGE_SOFT_NMS) has no IoU threshold")
+            merge_soft = (det_keys["MERGE_SOFT_NMS"],) + merge_soft[1:]
     torch.cuda.set_device(local_rank)
     if world > 1:       # results are gathered as host objects: gloo is enough, no GPU collective on this path
         torch.distributed.init_process_group("gloo")
@@ -181,7 +209,7 @@ def main():
         # DETECTION.MERGE_IOU_THRESHOLD (not a key of the reference): 0.5 when absent, null = no suppression (top-N per image)
         merge_iou = det.get("MERGE_IOU_THRESHOLD", 0.5)
         if rank == 0:
-            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou, vote_iou=merge_vote_iou)
+            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou, vote_iou=merge_vote_iou, soft=merge_soft)
 
     def merge_feed(hb, hs, hc, ids_, hw_last):
         merger.add(hb, hs, hc, ids_)

@@ -170,6 +170,51 @@ int mbx_merge_detections_voted(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, 
                                int32_t* out_src /*[I,max_det]*/, int32_t* out_count /*[I]*/,
                                int32_t* out_status /*[I]*/, int32_t* out_votes /*[I,max_det]*/, mbx_stream_t stream);
 
+/* SOFT-NMS in the per-image merge (Bodla et al. 2017; optional, off by default in detect.py): instead of deleting a
+ * candidate that overlaps a picked box, lower its score by a function of the IoU and let it compete again.  Inputs, the
+ * candidate set (slots [0, clamp(count[r], 0, k_max)) of the image's rows, flat index row * k_max + slot), out_status
+ * (1 above MBX_MERGE_MAX_CANDIDATES, out_count[i] = 0) and the unused output slots (0 / 0 / -1) are those of
+ * mbx_merge_detections.  Per image:
+ *   1. every candidate c has a working score t_c = (double)score_c.
+ *   2. c is LIVE iff t_c is finite and t_c > min_score.  A NaN, +-infinity and everything at or below min_score never
+ *      take part: they are not picked and decay nobody.  Weights are <= 1, so a candidate that leaves the live set never
+ *      returns.
+ *   3. repeat while fewer than max_det are picked and a live candidate exists:
+ *        PICK   the live candidate p with the largest t, bit-equal t resolved by ascending flat index.  The next output
+ *               slot gets p's box bytes, (float)t_p (round to nearest) and p's flat index.  p leaves the live set.
+ *        DECAY  for every live c: o = IoU(p, c) -- the float64 IoU of mbx_nms, term by term, with p as the EARLIER box
+ *               (iw = min(p.x2, c.x2) - max(p.x1, c.x1), ih alike; inter = iw > 0 && ih > 0 ? iw * ih : 0;
+ *               uni = area(p) + area(c) - inter; o = uni > 0 ? inter / uni : 0) -- then t_c = t_c * w, ONE rounded
+ *               multiply, with
+ *                 MBX_SOFT_LINEAR    w = o > iou_threshold ? 1.0 - o : 1.0
+ *                 MBX_SOFT_GAUSSIAN  w = exp(-(o * o) / sigma): one rounded product, one rounded division, a negation,
+ *                                    then exp (the device's float64 exp, documented to 1 ulp).  o == 0 gives exactly 1.
+ *               No fused multiply-add anywhere.
+ *   4. out_count[i] = the number of picks.  Picks come out in pick order; scores only fall, so out_scores is
+ *      non-increasing and the first max_det picks are exactly the max_det best of an uncut Soft-NMS.
+ * Linear: every operation is a single rounded float64 operation in a stated order, so all outputs are exact against a
+ * numpy restatement.  Gaussian: exact but for exp.
+ * vote_iou_threshold in (0, 1]: the vote launch of mbx_merge_detections_voted follows on the same stream -- its contract,
+ * out_votes and error bound unchanged; the voters' weights are the ORIGINAL scores, the kept boxes the picks.  0: no
+ * voting, out_votes is not touched (NULL iff vote_iou_threshold == 0).
+ * An image's outputs depend on its own rows only -- not on I, its place in the launch or the other images -- and the same
+ * input gives the same bytes on every call: each t_c is a product over the picks in pick order, whichever thread owns c.
+ * MBX_ERR_INVALID_ARG, nothing launched: a method other than 1 or 2; linear with a NaN iou_threshold; gaussian with sigma
+ * not finite or <= 0; min_score NaN, negative or infinite; vote_iou_threshold NaN or outside [0, 1]; vote_iou_threshold > 0
+ * with a null out_votes; any null pointer the plain merge rejects, I < 0, k_max <= 0, max_det <= 0.  max_det > 640:
+ * MBX_ERR_UNSUPPORTED, as for the other two entry points.  I == 0: MBX_OK, nothing launched.  iou_threshold is read by the
+ * linear method only, sigma by the gaussian only.  One workgroup per image; every pick is a pass over the image's live
+ * candidates.  Whether Soft-NMS raises AP on real data is NOT measured here: no trained model or dataset is at hand.  */
+#define MBX_SOFT_LINEAR 1
+#define MBX_SOFT_GAUSSIAN 2
+int mbx_merge_detections_soft(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const float* scores /*[R,k_max]*/,
+                              const int32_t* count /*[R]*/, const int32_t* image_rows /*[I+1] ascending*/, int I, int k_max,
+                              int max_det, int method, double iou_threshold /*linear only*/, double sigma /*gaussian only*/,
+                              double min_score, double vote_iou_threshold /*0 = no voting*/,
+                              double* out_boxes /*[I,max_det,4]*/, float* out_scores /*[I,max_det]*/,
+                              int32_t* out_src /*[I,max_det]*/, int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/,
+                              int32_t* out_votes /*[I,max_det]; NULL iff vote_iou_threshold == 0*/, mbx_stream_t stream);
+
 /* ------------------------------------------------------ COCO metric: matching (eval.py:212-226)
  * Replaces the matching step of the metric eval.py:212-226 runs: pycocotools' COCOeval.evaluateImg (iouType 'bbox',
  * useCats = 0, no crowd annotations), once per image, area range and IoU threshold; multibox_amd/cocoeval.py:_evaluate_img

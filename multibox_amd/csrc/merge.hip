@@ -1,4 +1,5 @@
-// libmbx: per-image merge of multi-crop detections (greedy NMS across patches + top-N), and box voting on what it keeps.
+// libmbx: per-image merge of multi-crop detections (greedy NMS across patches + top-N, or Soft-NMS), and box voting on
+// what it keeps.
 // The reference writes every patch's boxes one after the other (detect.py:408-460) and has no such stage; this one is
 // optional and sits behind mbx_decode_filter_topk (+ mbx_nms), reading exactly what they write.  Built with
 // -ffp-contract=off: the float64 IoU keeps the operation order of oracle.ref_numpy.nms_greedy, so keep decisions are exact.
@@ -270,6 +271,225 @@ vote_kernel(const double* __restrict__ boxes, const float* __restrict__ scores, 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- Soft-NMS
+// One workgroup of kSoftThreads per image; thread `tid` owns the candidates j = tid + k * kSoftThreads, k < kSoftPer, of
+// the image's list (rows in order, slots ascending: j ascending is flat index ascending).  Their working scores t live in
+// dynamic LDS, [kMaxCand] float64 = 128 KiB; their offsets from the image's first slot live in kSoftPer registers (the
+// 64 KiB a list of them would need do not fit beside the scores), indexed by the loop counter, which is uniform.
+constexpr int kSoftThreads = 1024;
+constexpr int kSoftWaves = kSoftThreads / 64;
+constexpr int kSoftPer = kMaxCand / kSoftThreads;
+constexpr int kSoftBatch = 2;                          // candidates whose box loads are issued together
+static_assert(kSoftPer * kSoftThreads == kMaxCand && kSoftPer % kSoftBatch == 0, "every candidate has an owner");
+
+// What a wavefront found: the order-preserving image of its best live score, whose that is, and its box.
+struct SoftBest { unsigned long long key; unsigned rel; unsigned pad; Box box; };
+
+// (key, rel) of a live candidate is better when its score is larger, of bit-equal scores when its flat index is lower.
+// A live t is positive and finite, so its bits order as u64 like the value; key 0 = nobody.
+__device__ __forceinline__ bool soft_better(unsigned long long ka, unsigned ra, unsigned long long kb, unsigned rb) {
+  return ka > kb || (ka == kb && ra < rb);
+}
+__device__ __forceinline__ bool soft_live(double t, double min_score) { return t > min_score && t < INFINITY; }
+
+// The weight of the definition (include/mbx.h) for an IoU o: every operation rounded once, in this order.
+template <int METHOD>
+__device__ __forceinline__ double soft_weight(double o, double thr, double sigma) {
+  if (METHOD == MBX_SOFT_LINEAR) return o > thr ? 1.0 - o : 1.0;
+  const double q = (o * o) / sigma;
+  return exp(-q);
+}
+
+//   1. candidate list as merge_kernel 1b, without the sort: offsets to LDS (in the room of the scores, which are not
+//      there yet), from there to the owners' registers; t = (double)score where that is live, else 0 (= not live, for
+//      good: a picked candidate gets it too).
+//   2. per pick: wave argmax by shuffles, the wave's winner writes (key, offset, box) to the wave's slot, ONE barrier,
+//      every thread reads the kSoftWaves slots and knows the pick (the slots alternate between two sets, so the next
+//      round's writes need no second barrier); thread 0 writes the pick out; then every thread decays its live
+//      candidates against the pick's box -- boxes re-read from global memory -- and tracks its best on the way.
+//      o == 0 gives the weight exactly 1 under both methods and is skipped.
+//   3. unused output slots 0 / 0 / -1.
+// t_c is a product over the picks in pick order whoever owns c, so the result is a function of the image's rows only.
+template <int METHOD>
+__global__ void __launch_bounds__(kSoftThreads)
+soft_merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ count,
+                  const int32_t* __restrict__ image_rows, int k_max, int max_det, double thr, double sigma, double min_score,
+                  double* __restrict__ out_boxes, float* __restrict__ out_scores, int32_t* __restrict__ out_src,
+                  int32_t* __restrict__ out_count, int32_t* __restrict__ out_status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char merge_lds[];
+  double* ts = reinterpret_cast<double*>(merge_lds);                                  // [kMaxCand]
+  unsigned* rel_list = reinterpret_cast<unsigned*>(merge_lds);                        // [kMaxCand], step 1 only
+  __shared__ int tile_cnt[kSoftThreads];
+  __shared__ int wave_tot[kSoftWaves];
+  __shared__ SoftBest wave_best[2][kSoftWaves];
+
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = image_rows[img], r1 = image_rows[img + 1];
+  const long long base = (long long)r0 * k_max;                 // flat index of the image's first slot
+  double* ob = out_boxes + (size_t)img * max_det * 4;
+  float* os = out_scores + (size_t)img * max_det;
+  int32_t* oi = out_src + (size_t)img * max_det;
+
+  // ---- 1a. number of candidates
+  int mine = 0;
+  for (int r = r0 + tid; r < r1; r += kSoftThreads) mine += min(max(count[r], 0), k_max);
+  mine = wave_sum(mine);
+  if (lane == 0) wave_tot[wave] = mine;
+  __syncthreads();
+  int total = 0;
+  for (int w = 0; w < kSoftWaves; ++w) total += wave_tot[w];
+  const bool too_many = total > kMaxCand;
+  if (too_many) total = 0;
+  total = __builtin_amdgcn_readfirstlane(total);
+
+  int nk = 0;
+  if (total > 0) {
+    // ---- 1b. offsets of the candidates, in list order
+    int off = 0;
+    for (int t0 = r0; t0 < r1; t0 += kSoftThreads) {
+      const int nrows = min(kSoftThreads, r1 - t0);
+      __syncthreads();                                           // the previous tile's counts have been read
+      if (tid < nrows) tile_cnt[tid] = min(max(count[t0 + tid], 0), k_max);
+      __syncthreads();
+      for (int q = 0; q < nrows; ++q) {
+        const int c = tile_cnt[q];
+        const unsigned rel0 = (unsigned)(t0 + q - r0) * (unsigned)k_max;
+        for (int s = tid; s < c; s += kSoftThreads) rel_list[off + s] = rel0 + (unsigned)s;
+        off += c;
+      }
+    }
+    __syncthreads();
+    unsigned rel[kSoftPer];
+#pragma unroll
+    for (int k = 0; k < kSoftPer; ++k) {
+      const int j = k * kSoftThreads + tid;
+      rel[k] = j < total ? rel_list[j] : 0xffffffffu;
+    }
+    __syncthreads();                                             // the offsets are in registers: the room is the scores' now
+
+    // ---- 1c. working scores, and the first argmax
+    unsigned long long bkey = 0ull;
+    unsigned brel = 0xffffffffu;
+    Box bbox = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < kSoftPer; ++k) {
+      const int j = k * kSoftThreads + tid;
+      if (k * kSoftThreads < total && j < total) {
+        double t = (double)scores[base + rel[k]];
+        if (!soft_live(t, min_score)) t = 0.0;
+        ts[j] = t;
+        const unsigned long long key = (unsigned long long)__double_as_longlong(t);
+        if (soft_better(key, rel[k], bkey, brel)) {
+          const double* p = boxes + (size_t)(base + rel[k]) * 4;
+          bkey = key; brel = rel[k];
+          bbox.x1 = p[0]; bbox.y1 = p[1]; bbox.x2 = p[2]; bbox.y2 = p[3];
+        }
+      }
+    }
+
+    // ---- 2. picks
+    for (;;) {
+      // the wave's best, every lane
+      unsigned long long wkey = bkey;
+      unsigned wrel = brel;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long ok = __shfl_xor(wkey, o, 64);
+        const unsigned orl = __shfl_xor(wrel, o, 64);
+        if (soft_better(ok, orl, wkey, wrel)) { wkey = ok; wrel = orl; }
+      }
+      SoftBest* slots = wave_best[nk & 1];
+      if (wkey == 0ull) {
+        if (lane == 0) { slots[wave].key = 0ull; slots[wave].rel = 0xffffffffu; }
+      } else if (brel == wrel) {                                 // one lane: offsets are distinct
+        slots[wave].key = wkey; slots[wave].rel = wrel; slots[wave].box = bbox;
+      }
+      __syncthreads();
+      int win = 0;
+      unsigned long long pkey = slots[0].key;
+      unsigned prel = slots[0].rel;
+#pragma unroll
+      for (int w = 1; w < kSoftWaves; ++w) {
+        const unsigned long long ok = slots[w].key;
+        const unsigned orl = slots[w].rel;
+        if (soft_better(ok, orl, pkey, prel)) { pkey = ok; prel = orl; win = w; }
+      }
+      if (pkey == 0ull) break;                                   // nobody is live
+      const Box pb = slots[win].box;
+      if (tid == 0) {
+        const long long flat = base + prel;
+        ob[nk * 4] = pb.x1; ob[nk * 4 + 1] = pb.y1; ob[nk * 4 + 2] = pb.x2; ob[nk * 4 + 3] = pb.y2;
+        os[nk] = (float)__longlong_as_double((long long)pkey);
+        oi[nk] = (int32_t)flat;
+      }
+      ++nk;
+      if (nk >= max_det) break;
+
+      // decay against the pick, and the next argmax
+      bkey = 0ull; brel = 0xffffffffu;
+      for (int k0 = 0; k0 < kSoftPer && k0 * kSoftThreads < total; k0 += kSoftBatch) {      // (uniform)
+        double t[kSoftBatch];
+        Box c[kSoftBatch];
+        bool live[kSoftBatch];
+#pragma unroll
+        for (int u = 0; u < kSoftBatch; ++u) {
+          const int j = (k0 + u) * kSoftThreads + tid;
+          t[u] = j < total ? ts[j] : 0.0;
+          live[u] = t[u] > 0.0;
+          c[u].x1 = c[u].y1 = c[u].x2 = c[u].y2 = 0.0;
+          if (live[u] && rel[k0 + u] == prel) {                  // the pick leaves the live set
+            ts[j] = 0.0;
+            live[u] = false;
+          }
+          if (live[u]) {
+            const double* p = boxes + (size_t)(base + rel[k0 + u]) * 4;
+            c[u].x1 = p[0]; c[u].y1 = p[1]; c[u].x2 = p[2]; c[u].y2 = p[3];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kSoftBatch; ++u) {
+          if (!live[u]) continue;
+          const int j = (k0 + u) * kSoftThreads + tid;
+          const double o = iou_corners(pb, c[u], box_area(c[u]));
+          double tn = t[u];
+          if (o != 0.0) {
+            tn = tn * soft_weight<METHOD>(o, thr, sigma);
+            if (!soft_live(tn, min_score)) tn = 0.0;
+            ts[j] = tn;
+          }
+          const unsigned long long key = (unsigned long long)__double_as_longlong(tn);
+          if (soft_better(key, rel[k0 + u], bkey, brel)) { bkey = key; brel = rel[k0 + u]; bbox = c[u]; }
+        }
+      }
+    }
+  }
+
+  // ---- 3. count, status and the unused slots
+  if (tid == 0) { out_count[img] = nk; out_status[img] = too_many ? 1 : 0; }
+  for (int t = nk + tid; t < max_det; t += kSoftThreads) {
+    ob[t * 4] = ob[t * 4 + 1] = ob[t * 4 + 2] = ob[t * 4 + 3] = 0.0;
+    os[t] = 0.f;
+    oi[t] = -1;
+  }
+}
+
+// The vote launches behind a kernel that has written the kept boxes and out_count (vote_kernel's grid: groups of
+// kVotePerBlock kept slots x at most 65 535 images).
+int launch_votes(const double* boxes, const float* scores, const int32_t* count, const int32_t* image_rows, int I, int k_max,
+                 int max_det, double vote_iou_threshold, double* out_boxes, const int32_t* out_count, int32_t* out_votes,
+                 mbx_stream_t stream) {
+  MBX_ENTER();
+  const int groups = (max_det + kVotePerBlock - 1) / kVotePerBlock;
+  for (int i0 = 0; i0 < I;) {
+    const int ni = I - i0 < 65535 ? I - i0 : 65535;                     // (the y extent of a grid)
+    hipLaunchKernelGGL(vote_kernel, dim3(groups, ni), dim3(kThreads), 0, mbx_s(stream), boxes, scores, count, image_rows,
+                       i0, k_max, max_det, vote_iou_threshold, out_boxes, out_count, out_votes);
+    MBX_LAUNCH_CHECK();
+    i0 += ni;
+  }
+  return MBX_OK;
+}
+
 }  // namespace
 
 extern "C" int mbx_merge_detections(const double* boxes, const float* scores, const int32_t* count,
@@ -304,14 +524,40 @@ extern "C" int mbx_merge_detections_voted(const double* boxes, const float* scor
   const int rc = mbx_merge_detections(boxes, scores, count, image_rows, I, k_max, max_det, iou_threshold, out_boxes,
                                       out_scores, out_src, out_count, out_status, stream);
   if (rc != MBX_OK || I == 0) return rc;
-  MBX_ENTER();
-  const int groups = (max_det + kVotePerBlock - 1) / kVotePerBlock;
-  for (int i0 = 0; i0 < I;) {
-    const int ni = I - i0 < 65535 ? I - i0 : 65535;                     // (the y extent of a grid)
-    hipLaunchKernelGGL(vote_kernel, dim3(groups, ni), dim3(kThreads), 0, mbx_s(stream), boxes, scores, count, image_rows,
-                       i0, k_max, max_det, vote_iou_threshold, out_boxes, out_count, out_votes);
-    MBX_LAUNCH_CHECK();
-    i0 += ni;
+  return launch_votes(boxes, scores, count, image_rows, I, k_max, max_det, vote_iou_threshold, out_boxes, out_count, out_votes,
+                      stream);
+}
+
+extern "C" int mbx_merge_detections_soft(const double* boxes, const float* scores, const int32_t* count,
+                                         const int32_t* image_rows, int I, int k_max, int max_det, int method,
+                                         double iou_threshold, double sigma, double min_score, double vote_iou_threshold,
+                                         double* out_boxes, float* out_scores, int32_t* out_src, int32_t* out_count,
+                                         int32_t* out_status, int32_t* out_votes, mbx_stream_t stream) {
+  if (!boxes || !scores || !count || !image_rows || !out_boxes || !out_scores || !out_src || !out_count || !out_status)
+    return MBX_ERR_INVALID_ARG;
+  if (I < 0 || k_max <= 0 || max_det <= 0) return MBX_ERR_INVALID_ARG;
+  if (method == MBX_SOFT_LINEAR) {
+    if (isnan(iou_threshold)) return MBX_ERR_INVALID_ARG;
+  } else if (method == MBX_SOFT_GAUSSIAN) {
+    if (!(sigma > 0.0 && sigma < INFINITY)) return MBX_ERR_INVALID_ARG;                            // a NaN too
+  } else {
+    return MBX_ERR_INVALID_ARG;
   }
-  return MBX_OK;
+  if (!(min_score >= 0.0 && min_score < INFINITY)) return MBX_ERR_INVALID_ARG;                     // a NaN too
+  if (!(vote_iou_threshold >= 0.0 && vote_iou_threshold <= 1.0)) return MBX_ERR_INVALID_ARG;       // a NaN too
+  const bool vote = vote_iou_threshold > 0.0;
+  if (vote && !out_votes) return MBX_ERR_INVALID_ARG;
+  if (max_det > kMergeMaxDet) return MBX_ERR_UNSUPPORTED;
+  if (I == 0) return MBX_OK;
+  const size_t lds = (size_t)kMaxCand * sizeof(double);
+  const auto kernel = method == MBX_SOFT_LINEAR ? soft_merge_kernel<MBX_SOFT_LINEAR> : soft_merge_kernel<MBX_SOFT_GAUSSIAN>;
+  MBX_ENTER();
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess) return MBX_ERR_LAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(I), dim3(kSoftThreads), lds, mbx_s(stream), boxes, scores, count, image_rows, k_max, max_det,
+                     iou_threshold, sigma, min_score, out_boxes, out_scores, out_src, out_count, out_status);
+  MBX_LAUNCH_CHECK();
+  if (!vote) return MBX_OK;
+  return launch_votes(boxes, scores, count, image_rows, I, k_max, max_det, vote_iou_threshold, out_boxes, out_count, out_votes,
+                      stream);
 }

@@ -115,12 +115,19 @@ class ImageMerger:
     vote_iou None: the kept boxes are the kept candidates' own (mbx_merge_detections, as ever).  A float in (0, 1]: box
     voting (mbx_merge_detections_voted) -- the same kept list and scores, every kept box replaced by the score-weighted
     mean of all candidates of its image with IoU >= vote_iou against it.  An image above 16 384 candidates is still cut
-    to its best 16 384 on the host first, and only those vote."""
+    to its best 16 384 on the host first, and only those vote.
+    soft None: greedy suppression, as above.  ("linear" | "gaussian", sigma, min_score) (records.merge_soft_nms checks it):
+    Soft-NMS (mbx_merge_detections_soft) -- an overlapping candidate's score is lowered instead of the candidate deleted,
+    the scores that come out are the decayed ones, in pick order.  Linear takes iou_threshold as its threshold (None is a
+    ValueError), gaussian ignores it; vote_iou is passed through.  The host-side cut above 16 384 candidates comes first."""
 
-    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256, vote_iou=None):
+    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256, vote_iou=None, soft=None):
         self.K, self.max_det = int(k_max), int(max_detections)
         self.thr = float("inf") if iou_threshold is None else float(iou_threshold)
         self.vote_iou = REC.merge_vote_iou(vote_iou)
+        self.soft = None if soft is None else REC.merge_soft_nms(*soft)
+        if self.soft is not None and self.soft[0] == REC.SOFT_NMS_METHODS["linear"] and (iou_threshold is None or self.thr != self.thr):
+            raise ValueError("linear Soft-NMS needs an IoU threshold (scores decay above it), not %r" % (iou_threshold,))
         self.device, self.flush_images = device, max(1, int(flush_images))
         self.stream = torch.cuda.Stream(device=device)      # its uploads and launches do not queue behind the detect loop
         self._rows, self._ids, self._runs = [], [], 0
@@ -177,7 +184,20 @@ class ImageMerger:
             o_src = torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
             o_count = torch.empty((n_img,), dtype=torch.int32, device=self.device)
             o_status = torch.empty((n_img,), dtype=torch.int32, device=self.device)
-            if self.vote_iou is None:
+            call = "mbx_merge_detections" if self.vote_iou is None else "mbx_merge_detections_voted"
+            if self.soft is not None:
+                call = "mbx_merge_detections_soft"
+                method, sigma, min_score = self.soft
+                o_votes = None if self.vote_iou is None else torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
+                _lib.check(_lib.lib().mbx_merge_detections_soft(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
+                                                                d_rows.data_ptr(), n_img, self.K, self.max_det, method,
+                                                                self.thr if method == 1 else 0.0, sigma, min_score,
+                                                                0.0 if self.vote_iou is None else self.vote_iou,
+                                                                o_boxes.data_ptr(), o_scores.data_ptr(), o_src.data_ptr(),
+                                                                o_count.data_ptr(), o_status.data_ptr(),
+                                                                None if o_votes is None else o_votes.data_ptr(),
+                                                                self.stream.cuda_stream), call)
+            elif self.vote_iou is None:
                 _lib.check(_lib.lib().mbx_merge_detections(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
                                                            d_rows.data_ptr(), n_img, self.K, self.max_det, self.thr,
                                                            o_boxes.data_ptr(), o_scores.data_ptr(), o_src.data_ptr(),
@@ -193,7 +213,7 @@ class ImageMerger:
                            "mbx_merge_detections_voted")
             status = o_status.cpu().numpy()
             if status.any():
-                raise _lib.MbxError("mbx_merge_detections: status %d for image %r" % (int(status.max()), ids[int(np.argmax(status != 0))]))
+                raise _lib.MbxError("%s: status %d for image %r" % (call, int(status.max()), ids[int(np.argmax(status != 0))]))
             self._out.append((ids, o_boxes.cpu().numpy(), o_scores.cpu().numpy(), o_count.cpu().numpy()))
 
     def finish(self):

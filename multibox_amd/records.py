@@ -48,6 +48,35 @@ def merge_vote_iou(value):
     return v
 
 
+SOFT_NMS_METHODS = {"linear": 1, "gaussian": 2}      # MBX_SOFT_LINEAR, MBX_SOFT_GAUSSIAN (include/mbx.h)
+
+
+def merge_soft_nms(method, sigma=0.5, min_score=0.001):
+    """DETECTION.MERGE_SOFT_NMS, MERGE_SOFT_NMS_SIGMA and MERGE_SOFT_NMS_MIN_SCORE / ImageMerger(soft=): method None = no
+    Soft-NMS (None is returned), else "linear" or "gaussian" and the validated (method id, sigma, min_score) that
+    mbx_merge_detections_soft accepts: sigma a finite number > 0 (the width of the Gaussian weight exp(-IoU^2 / sigma); read
+    by the gaussian method only, checked for both), min_score a finite number >= 0 (a candidate whose decayed score is at or
+    below it is dropped).  Anything else, bools included, is a ValueError."""
+    if method is None:
+        return None
+    if not isinstance(method, str) or method not in SOFT_NMS_METHODS:
+        raise ValueError("the Soft-NMS method must be 'linear', 'gaussian' or null (no Soft-NMS), not %r" % (method,))
+
+    def number(value):
+        try:
+            return float("nan") if isinstance(value, bool) else float(value)
+        except (TypeError, ValueError):
+            return float("nan")
+    sg, ms = number(sigma), number(min_score)
+    if not (0.0 < sg < float("inf")):
+        raise ValueError("the Soft-NMS sigma (width of the Gaussian weight exp(-IoU^2 / sigma)) must be a finite number > 0, "
+                         "not %r" % (sigma,))
+    if not (0.0 <= ms < float("inf")):
+        raise ValueError("the Soft-NMS minimum score (decayed scores at or below it are dropped) must be a finite number "
+                         ">= 0, not %r" % (min_score,))
+    return SOFT_NMS_METHODS[method], sg, ms
+
+
 def group_rows(image_ids):
     """Runs of equal consecutive ids in stream order: (ids, image_rows [len(ids) + 1] int32); image i owns the rows
     [image_rows[i], image_rows[i + 1]).  An id that returns later is a new image; the padding rows of a partial batch

@@ -90,6 +90,36 @@ int mbx_loss_fwd_bwd(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B
                      float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
                      void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
+/* mbx_loss_fwd_bwd with HARD-NEGATIVE MINING (SSD, Liu et al. 2016, section 2.2; optional, not in the reference, off unless
+ * the caller asks): per image only the highest-scoring negatives count, a fixed number per positive; the others contribute
+ * neither loss nor gradient.  Every argument up to d_logits is mbx_loss_fwd_bwd's, same order and meaning.  Per image b:
+ *   n_pos = number of p with match[b,p] >= 0;  N_neg = P - n_pos
+ *   K     = min(N_neg, max(min_neg, neg_per_pos * n_pos)), the product in 64 bits: integer arithmetic, exact
+ *   the candidates are the negatives (match[b,p] < 0), ordered by the order-preserving image of conf_in[b,p] -- THE FLOAT
+ *   PASSED IN: the logit when conf_is_logit = 1, the confidence otherwise; both are monotone in the negative's loss, and the
+ *   order then does not depend on the device's expf / logf -- descending, bit-equal images by ascending p.  It is the image
+ *   mbx_decode_filter_topk sorts by: -0 == +0, a NaN ranks first (a NaN negative is taken whenever K > 0 and makes
+ *   conf_loss NaN, as in mbx_loss_fwd_bwd).  The first K candidates are SELECTED;  n_neg[b] = K (n_neg may be NULL).
+ * Positives and selected negatives get exactly the terms and gradients of mbx_loss_fwd_bwd.  An unselected negative adds
+ * nothing to conf_loss and its d_logits is +0.0f.  d_raw_locs and loss2[0] do not depend on the selection.  Nothing is
+ * normalised by n_pos: the loss stays a batch sum and grad_scale the caller's.
+ * If K == N_neg for every image (min_neg >= P, say), loss2, d_raw_locs and d_logits are byte-identical to
+ * mbx_loss_fwd_bwd on the same inputs (same per-thread stride, same reduction order).  An image's outputs depend on its
+ * own row only -- not on B or its place in the launch -- and the same input gives the same bytes on every call (no
+ * floating-point atomics).  No limit on P: the K-th candidate is found by a radix select over the row, not by a sort.
+ * neg_per_pos < 1, min_neg < 0 or anything mbx_loss_fwd_bwd rejects: MBX_ERR_INVALID_ARG; workspace_bytes <
+ * mbx_loss_mined_workspace_bytes(B, P): MBX_ERR_WORKSPACE; nothing is launched or written either way.  Two launches on
+ * `stream`, one workgroup per image.
+ * What mining does to AP on real data is NOT measured here: no trained model or dataset is at hand.                  */
+size_t mbx_loss_mined_workspace_bytes(int B, int P);
+int mbx_loss_fwd_bwd_mined(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B,P]*/,
+                           int conf_is_logit, const float* gt /*[B,G,4]*/,
+                           const int32_t* match /*[B,P]*/, float alpha, float grad_scale, int B, int P,
+                           int G, float* loss2 /*[2]*/,
+                           float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
+                           int neg_per_pos, int min_neg, int32_t* n_neg /*[B] or NULL*/,
+                           void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
 /* ------------------------------------------------- detect post-processing (A9-A12)
  * Replaces the per-patch numpy loop detect.py:408-436: decode + clip [0,1]
  * (412-413), filter_proposals (74-104, strict inequalities), sort by confidence

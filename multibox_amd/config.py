@@ -46,3 +46,26 @@ def with_defaults(cfg):
     for k, v in cfg.items():
         out[k] = v
     return out
+
+
+def _int_key(cfg, key, minimum):
+    """cfg[key] as an int >= minimum.  A float without a fraction counts (3.0); a bool, a float with a fraction, a string
+    or anything else raises ValueError naming the key."""
+    v = cfg[key]
+    ok = isinstance(v, (int, float)) and not isinstance(v, bool) and minimum <= v <= 2 ** 31 - 1 and v == int(v)
+    if not ok:
+        raise ValueError("%s must be an integer in [%d, 2^31), got %r" % (key, minimum, v))
+    return int(v)
+
+
+def negative_mining(cfg):
+    """Hard-negative mining for the confidence loss (mbx_loss_fwd_bwd_mined; not in the reference, so off when absent):
+    None, or (neg_per_pos, min_neg) from LOSS_NEG_PER_POS (an int >= 1; absent or null = off) and LOSS_MIN_NEG (an int
+    >= 0, default 0; only with LOSS_NEG_PER_POS).  Per image the max(min_neg, neg_per_pos * positives) highest-scoring
+    negatives are kept.  Raises ValueError naming the key.  Host code only."""
+    if cfg.get("LOSS_NEG_PER_POS") is None:
+        if cfg.get("LOSS_MIN_NEG") is not None:
+            raise ValueError("LOSS_MIN_NEG is given without LOSS_NEG_PER_POS")
+        return None
+    neg_per_pos = _int_key(cfg, "LOSS_NEG_PER_POS", 1)
+    return neg_per_pos, (_int_key(cfg, "LOSS_MIN_NEG", 0) if cfg.get("LOSS_MIN_NEG") is not None else 0)

@@ -254,6 +254,132 @@ __global__ void loss_final_kernel(const double* __restrict__ partial, int B, flo
   }
 }
 
+// ------------------------------------------------- loss with hard-negative mining
+// Composite key of a negative: the order-preserving image of its input float (score_order_key) above the INVERTED index
+// P-1-p, so that unsigned order = (score descending, p ascending) and no two candidates are equal.
+__device__ __forceinline__ unsigned long long mined_key(float conf_in, int P, int p) {
+  return ((unsigned long long)score_order_key(conf_in) << 32) | (unsigned)(P - 1 - p);
+}
+
+// loss_kernel with only the K highest-ranked negatives of each image counted (mbx_loss_fwd_bwd_mined, mbx.h).  One
+// workgroup per image.  The K-th largest composite key -- the cut -- is found by a radix select: per 8-bit digit, most
+// significant first, a 256-bin LDS histogram of the candidates that still share the digits fixed so far, then one wave
+// walks the bins from the top to the one that holds the K-th.  No sort, nothing held per thread: any P.  A pass re-reads
+// the row (2.6-26 KB: L1 / L2 hits).  The select ends as soon as the bin it lands in is taken whole (its count is what is
+// still needed): with distinct scores that is after 3-4 passes, and at once when K is 0 or every negative is taken.  Index
+// digits above the bits of P-1 are zero for every candidate and are skipped.  The last pass is loss_kernel's loop, same
+// stride, same reduction, with "negative and below the cut -> no loss, +0 gradient": byte-identical to it when all are taken.
+__global__ void __launch_bounds__(kThreads)
+loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                  int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
+                  float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+  static_assert(kThreads == 256, "one thread per histogram bin, four bins per lane of the walking wave");
+  __shared__ unsigned hist[256];
+  __shared__ unsigned long long sh_cut;
+  __shared__ int sh_need, sh_done;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int* mt = match + (size_t)b * P;
+  const float* cf = logits + (size_t)b * P;
+
+  unsigned long long cut = 0ull;     // the digits fixed so far, zeros below
+  int need = 0;                      // candidates still to take among those that share them
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    if (shift < 32 && ((unsigned)(P - 1) >> shift) == 0) continue;
+    const unsigned long long fixed = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int p = tid; p < P; p += kThreads) {
+      if (mt[p] >= 0) continue;
+      const unsigned long long key = mined_key(cf[p], P, p);
+      if (((key ^ cut) & fixed) == 0ull) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {                  // lane l owns bins 4l .. 4l+3; `incl` = candidates in its bins and all higher ones
+      const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+      const unsigned own = h0 + h1 + h2 + h3;
+      unsigned incl = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_down(incl, o, 64);
+        if (tid + o < 64) incl += t;
+      }
+      bool whole = false;            // the answer is known without looking at a bin: nothing, or every negative
+      if (shift == 56) {             // first pass: every negative was counted
+        const int n_negatives = (int)__shfl(incl, 0, 64), n_pos = P - n_negatives;
+        long long K = (long long)neg_per_pos * (long long)n_pos;
+        if (K < (long long)min_neg) K = min_neg;
+        if (K > (long long)n_negatives) K = n_negatives;
+        need = (int)K;
+        whole = need == 0 || need == n_negatives;
+        if (tid == 0) {
+          if (n_neg) n_neg[b] = need;
+          if (whole) { sh_cut = need == 0 ? ~0ull : 0ull; sh_need = 0; sh_done = 1; }   // no key is all ones: index < 2^31
+        }
+      }
+      const unsigned above = incl - own, k = (unsigned)need;
+      if (!whole && above < k && k <= incl) {                 // exactly one lane: the K-th lies in one of its four bins
+        unsigned a = above, cnt = h3;
+        int d = 3;
+        if (k > a + h3) { a += h3; cnt = h2; d = 2;
+          if (k > a + h2) { a += h2; cnt = h1; d = 1;
+            if (k > a + h1) { a += h1; cnt = h0; d = 0; } } }
+        sh_cut = cut | ((unsigned long long)(4 * tid + d) << shift);
+        sh_need = (int)(k - a);
+        sh_done = cnt == k - a;
+      }
+    }
+    __syncthreads();
+    cut = sh_cut;
+    need = sh_need;
+    if (sh_done) break;
+  }
+
+  double loc_acc = 0.0, conf_acc = 0.0;
+  for (int p = tid; p < P; p += kThreads) {
+    const size_t i = (size_t)b * P + p;
+    const int m = match[i];
+    const float z = logits[i];
+    float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
+    float g;
+    if (m < 0 && mined_key(z, P, p) < cut) {
+      g = 0.f;                                              // an unselected negative: no loss, +0 whatever grad_scale is
+    } else {
+      const float s = is_logit ? 1.0f / (1.0f + expf(-z)) : z;
+      const float c = __fadd_rn(s, 1e-10f);                  // loss.py:74
+      const float ds = is_logit ? s * (1.0f - s) : 1.0f;
+      float dz;
+      if (m >= 0) {
+        const float4 l = decoded[i], q = gt[(size_t)b * G + m];
+        const float d0 = __fsub_rn(l.x, q.x), d1 = __fsub_rn(l.y, q.y), d2 = __fsub_rn(l.z, q.z), d3 = __fsub_rn(l.w, q.w);
+        loc_acc += (double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2 + (double)d3 * d3;   // loss.py:100
+        conf_acc -= (double)logf(c);                                                      // loss.py:101
+        const float a = alpha * grad_scale;
+        dl = make_float4(a * d0, a * d1, a * d2, a * d3);
+        dz = -ds / c;
+      } else {
+        const float w = __fadd_rn(__fsub_rn(1.0f, c), 1e-10f);
+        conf_acc -= (double)logf(w);
+        dz = ds / w;
+      }
+      g = dz * grad_scale;
+    }
+    if (d_locs) d_locs[i] = dl;
+    if (d_logits) d_logits[i] = g;
+  }
+  loc_acc = wave_sum(loc_acc);
+  conf_acc = wave_sum(conf_acc);
+  __shared__ double red[kWaves][2];
+  if ((tid & 63) == 0) { red[tid >> 6][0] = loc_acc; red[tid >> 6][1] = conf_acc; }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, c = 0.0;
+    for (int w = 0; w < kWaves; ++w) { a += red[w][0]; c += red[w][1]; }
+    partial[2 * b] = a;
+    partial[2 * b + 1] = c;
+  }
+}
+
 // ------------------------------------------------------- decode + filter + top-K
 // Key: kept flag (bit 63) | order-preserving image of the confidence's float bits (32 bits) | prediction index
 // (31 bits); bitonic sort, descending.  The float image (score_order_key, boxes.h) orders ANY float like a comparison
@@ -381,6 +507,27 @@ extern "C" int mbx_loss_fwd_bwd(const float* decoded, const float* logits, int c
   hipLaunchKernelGGL(loss_kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream),
                      reinterpret_cast<const float4*>(decoded), logits, conf_is_logit,
                      reinterpret_cast<const float4*>(gt), match, alpha, grad_scale, P, G, partial, reinterpret_cast<float4*>(d_raw_locs), d_logits);
+  MBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" size_t mbx_loss_mined_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+
+extern "C" int mbx_loss_fwd_bwd_mined(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                      const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                      float* d_raw_locs, float* d_logits, int neg_per_pos, int min_neg, int32_t* n_neg,
+                                      void* workspace, size_t workspace_bytes, mbx_stream_t stream) {
+  if (!decoded || !logits || !gt || !match || !loss2 || B <= 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (neg_per_pos < 1 || min_neg < 0) return MBX_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < mbx_loss_mined_workspace_bytes(B, P)) return MBX_ERR_WORKSPACE;
+  double* partial = reinterpret_cast<double*>(workspace);
+  MBX_ENTER();
+  hipLaunchKernelGGL(loss_mined_kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream),
+                     reinterpret_cast<const float4*>(decoded), logits, conf_is_logit,
+                     reinterpret_cast<const float4*>(gt), match, alpha, grad_scale, P, G, neg_per_pos, min_neg, partial,
+                     reinterpret_cast<float4*>(d_raw_locs), d_logits, n_neg);
   MBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
   MBX_LAUNCH_CHECK();

@@ -61,9 +61,14 @@ def compute_assignments(locations, confidences, gt_bboxes, num_gt_bboxes, batch_
 
 
 class MultiboxLoss:
-    """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step)."""
+    """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step).
 
-    def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda"):
+    neg_per_pos (an int >= 1; None = off, the reference's loss): hard-negative mining -- per image only the
+    max(min_neg, neg_per_pos * positives) highest-scoring negatives count (mbx_loss_fwd_bwd_mined, include/mbx.h);
+    their number per image is left in ``n_neg``.  What that does to AP on real data is not measured here."""
+
+    def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
+                 min_neg=0):
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
         self.P = self.priors.shape[0]
         self.B, self.G, self.alpha = int(batch_size), int(max_num_bboxes), float(location_loss_alpha)
@@ -75,7 +80,12 @@ class MultiboxLoss:
         self.loss2 = torch.zeros((2,), **f)
         self.d_locs = torch.empty((self.B, self.P, 4), **f)
         self.d_logits = torch.empty((self.B, self.P), **f)
-        self.ws = torch.empty((_lib.lib().mbx_loss_workspace_bytes(self.B),), dtype=torch.uint8, device=device)
+        self.neg_per_pos, self.min_neg, self.n_neg = neg_per_pos, min_neg, None
+        ws_bytes = _lib.lib().mbx_loss_workspace_bytes(self.B)
+        if neg_per_pos is not None:
+            self.n_neg = torch.zeros((self.B,), dtype=torch.int32, device=device)
+            ws_bytes = _lib.lib().mbx_loss_mined_workspace_bytes(self.B, self.P)
+        self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
 
     def forward_backward(self, raw_locs, logits, gt_bboxes, num_gt_bboxes, grad_scale=1.0, conf_is_logit=True):
         """raw_locs [B,P,4], logits [B,P] f32 -> (loss2 [2] = {location_loss, confidence_loss}, d_locs, d_logits)."""
@@ -93,10 +103,18 @@ class MultiboxLoss:
         _lib.check(l.mbx_match(self.decoded.data_ptr(), self.conf.data_ptr(), _f32(gt_bboxes).data_ptr(),
                                _i32(num_gt_bboxes).data_ptr(), self.alpha, B, P, G, self.match.data_ptr(),
                                self.status.data_ptr(), None, 0, s), "mbx_match")
-        _lib.check(l.mbx_loss_fwd_bwd(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
-                                      gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
-                                      B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(), self.d_logits.data_ptr(),
-                                      self.ws.data_ptr(), self.ws.numel(), s), "mbx_loss_fwd_bwd")
+        if self.neg_per_pos is None:
+            _lib.check(l.mbx_loss_fwd_bwd(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
+                                          gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
+                                          B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(), self.d_logits.data_ptr(),
+                                          self.ws.data_ptr(), self.ws.numel(), s), "mbx_loss_fwd_bwd")
+        else:
+            _lib.check(l.mbx_loss_fwd_bwd_mined(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
+                                                gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
+                                                B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
+                                                self.d_logits.data_ptr(), self.neg_per_pos, self.min_neg,
+                                                self.n_neg.data_ptr(), self.ws.data_ptr(), self.ws.numel(), s),
+                       "mbx_loss_fwd_bwd_mined")
         return self.loss2, self.d_locs, self.d_logits
 
 

@@ -1,0 +1,71 @@
+"""mbx_loss_fwd_bwd against mbx_loss_fwd_bwd_mined (hard-negative mining, neg_per_pos = 3) at the headline shape (64 images,
+P = 646, G = 13) and the 512x512 shape (P = 3199, G = 100): what the selection costs on top of the loss it feeds.
+
+Both entry points run in one process on the same buffers.  A call is two launches of a few microseconds, so a host loop
+would time the enqueue: CALLS calls of each are captured into a graph of their own, both graphs are warmed up, then
+replayed alternately for ROUNDS rounds, each replay between a pair of device events.  Reported: the median time per call
+and its range over the rounds, and the ratio of the medians.  What mining does to AP is not measured: that needs a dataset.
+usage: python tools/loss_bench.py"""
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+CALLS, ROUNDS, NEG_PER_POS = 2000, 15, 3
+
+if __name__ == "__main__":
+    import numpy as np, torch
+    import __graft_entry__ as g
+    g.build()
+    from multibox_amd import _lib
+    l = _lib.lib()
+    for B, P, G in ((64, 646, 13), (64, 3199, 100)):
+        rng = np.random.RandomState(P)
+        n_pos = rng.randint(1, G + 1, B)
+        n_pos[0], n_pos[1] = G, 0
+        match = -np.ones((B, P), np.int32)
+        for b in range(B):
+            match[b, rng.permutation(P)[:n_pos[b]]] = rng.permutation(G)[:n_pos[b]]
+        match = torch.from_numpy(match).cuda()
+        dec = torch.from_numpy(rng.uniform(0, 1, (B, P, 4)).astype(np.float32)).cuda()
+        logits = torch.from_numpy((rng.randn(B, P) * 2 - 2).astype(np.float32)).cuda()
+        gt = torch.from_numpy(rng.uniform(0, 1, (B, G, 4)).astype(np.float32)).cuda()
+        f = dict(dtype=torch.float32, device="cuda")
+        loss2, dl, dz = torch.zeros(2, **f), torch.zeros(B, P, 4, **f), torch.zeros(B, P, **f)
+        n_neg = torch.zeros(B, dtype=torch.int32, device="cuda")
+        ws = torch.empty(max(l.mbx_loss_workspace_bytes(B), l.mbx_loss_mined_workspace_bytes(B, P)), dtype=torch.uint8, device="cuda")
+        head = (dec.data_ptr(), logits.data_ptr(), 1, gt.data_ptr(), match.data_ptr(), 1000.0, 1.0, B, P, G, loss2.data_ptr(),
+                dl.data_ptr(), dz.data_ptr())
+        tail = (ws.data_ptr(), ws.numel())
+
+        def plain():
+            _lib.check(l.mbx_loss_fwd_bwd(*head, *tail, torch.cuda.current_stream().cuda_stream), "mbx_loss_fwd_bwd")
+
+        def mined():
+            _lib.check(l.mbx_loss_fwd_bwd_mined(*head, NEG_PER_POS, 0, n_neg.data_ptr(), *tail,
+                                                torch.cuda.current_stream().cuda_stream), "mbx_loss_fwd_bwd_mined")
+        graphs = {}
+        for name, fn in (("unmined", plain), ("mined", mined)):
+            fn()                                               # lazy code-object load, outside the capture
+            torch.cuda.synchronize()
+            graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[name]):
+                for _ in range(CALLS):
+                    fn()
+        for _ in range(3):
+            for gr in graphs.values():
+                gr.replay()
+        torch.cuda.synchronize()
+        kept = n_neg.float().mean().item()
+        times = {name: [] for name in graphs}
+        for _ in range(ROUNDS):
+            for name, gr in graphs.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                gr.replay()
+                b.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(b) / CALLS * 1e3)
+        med = {name: float(np.median(t)) for name, t in times.items()}
+        print("B=%d P=%d G=%d neg_per_pos=%d (%.1f of %.1f negatives kept per image): " % (B, P, G, NEG_PER_POS, kept, P - n_pos.mean())
+              + "  ".join("%s %.2f us (%.2f..%.2f)" % (name, med[name], min(t), max(t)) for name, t in times.items())
+              + "  mined / unmined = %.2f  [median of %d graph replays of %d calls each, alternating]" % (
+                  med["mined"] / med["unmined"], ROUNDS, CALLS), flush=True)

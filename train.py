@@ -41,7 +41,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -63,6 +63,10 @@ def main():
         raise SystemExit("give --tfrecords FILE... or --synthetic")
     if args.pretrained_model and not os.path.exists(args.pretrained_model):
         raise SystemExit("pretrained model not found: %s" % args.pretrained_model)
+    try:                                          # [new] LOSS_NEG_PER_POS / LOSS_MIN_NEG: hard-negative mining, off when absent
+        mining = negative_mining(cfg)
+    except ValueError as e:
+        raise SystemExit("config: %s" % e)
     torch.cuda.set_device(local_rank)
     pg = None
     if world > 1:
@@ -81,7 +85,8 @@ def main():
                  decay_steps_=decay_steps(cfg.NUM_TRAIN_EXAMPLES, cfg.BATCH_SIZE * world, cfg.NUM_EPOCHS_PER_DELAY),
                  learning_rate_decay_factor=cfg.LEARNING_RATE_DECAY_FACTOR, staircase=cfg.LEARNING_RATE_STAIRCASE,
                  rmsprop_decay=cfg.RMSPROP_DECAY, rmsprop_momentum=float(cfg.RMSPROP_MOMENTUM), rmsprop_epsilon=cfg.RMSPROP_EPSILON,
-                 moving_average_decay=cfg.MOVING_AVERAGE_DECAY, process_group=pg, trainable_scopes=args.trainable_scopes)
+                 moving_average_decay=cfg.MOVING_AVERAGE_DECAY, process_group=pg, trainable_scopes=args.trainable_scopes,
+                 neg_per_pos=mining[0] if mining else None, min_neg=mining[1] if mining else 0)
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -168,6 +173,8 @@ def main():
             ips = cfg.BATCH_SIZE * world * (tr.global_step - step0) / (now - t_log) if now > t_log else 0.0
             rec = dict(global_step=tr.global_step, total_loss=total, location_loss=loc, confidence_loss=conf,
                        learning_rate=tr.lr, images_per_sec=ips)          # train.py:266-271 summaries
+            if mining:
+                rec["mined_negatives_per_image"] = tr.mined_negatives_per_image()
             print("global step %d: loss = %.4f (loc %.4f conf %.4f) lr %.6f %.1f img/s" % (tr.global_step, total, loc, conf, tr.lr, ips))
             log.write(json.dumps(rec) + "\n")
             log.flush()

@@ -73,6 +73,39 @@ int mbx_match(const float* decoded /*[B,P,4]*/, const float* conf /*[B,P]*/,
               int B, int P, int G, int32_t* match /*[B,P]*/, int32_t* status /*[B]*/,
               void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
+/* THRESHOLD MATCHING behind mbx_match (SSD, Liu et al. 2016, section 2.2, "matching strategy"; optional, not in the
+ * reference, off unless the caller asks).  mbx_match is bipartite: every box gets exactly one prior.  This step then gives
+ * every prior that is still free to the box it overlaps most, if that overlap is over a threshold, so that priors which sit
+ * squarely on an object are trained as positives and not as background.  `priors` are the PRIORS themselves as corners
+ * (x1, y1, x2, y2), not the decoded predictions; `match` is mbx_match's output and is updated in place.  Per image b, with
+ * n = n_gt[b]:
+ *   status[b] != 0 or n <= 0 (or n > G, which mbx_match never leaves with status 0): the image is SKIPPED, its row of
+ *   `match` stays byte for byte as it was and n_extra[b] = 0.
+ *   Otherwise, for every prior p with match[b,p] < 0 and every box j in [0, n): the IoU in float64 on the float32 inputs
+ *   widened to double, in this term order (the prior first):
+ *     iw = min(p.x2, j.x2) - max(p.x1, j.x1), ih likewise;  inter = iw > 0 && ih > 0 ? iw * ih : 0
+ *     area = (x2 - x1) * (y2 - y1);  uni = area_p + area_j - inter;  iou = uni > 0 ? inter / uni : 0
+ *   best_j = the j with the largest iou, the lowest such j among equals.  If iou(p, best_j) > (double)iou_threshold --
+ *   strictly -- match[b,p] = best_j.  (An IoU that is NaN, which takes a non-finite prior, is over no threshold.)
+ *   A prior that mbx_match assigned keeps its box, even where another box overlaps it more.  Rows j >= n of `gt` are
+ *   padding and are never read: a NaN there changes nothing.
+ *   n_extra[b] = the number of priors newly assigned in image b.  Every n_extra[b] is written on every call (no memset by
+ *   the caller); n_extra may be NULL.
+ * An image's row depends on its own inputs only -- not on B or its place in the launch -- and the same input gives the same
+ * bytes on every call (no floating-point atomics, the count is a wave and LDS reduction).  With iou_threshold = 1.0f no IoU
+ * can exceed it: `match` comes back byte-identical and n_extra all zero.
+ * NULL priors / gt / n_gt / status / match, B < 0, P <= 0, G <= 0 or an iou_threshold not in (0, 1] (NaN included):
+ * MBX_ERR_INVALID_ARG; G > 1536 (the staged boxes, 40 bytes each, would not fit the LDS of a plain launch):
+ * MBX_ERR_UNSUPPORTED; nothing is launched or written either way.  B == 0: MBX_OK.  One launch on `stream`, one workgroup
+ * per image, no workspace, graph-capturable.  mbx_loss_fwd_bwd and mbx_loss_fwd_bwd_mined read the extended `match` as
+ * they read any other; mining counts its positives from it, so its budget grows with the priors added here.
+ * What threshold matching does to AP on real data is NOT measured here: no trained model or dataset is at hand.          */
+int mbx_match_extend(const float* priors /*[P,4] x1,y1,x2,y2*/, const float* gt /*[B,G,4]*/,
+                     const int32_t* n_gt /*[B]*/, const int32_t* status /*[B], as mbx_match left it*/,
+                     float iou_threshold, int B, int P, int G,
+                     int32_t* match /*[B,P] IN/OUT: mbx_match's output*/,
+                     int32_t* n_extra /*[B] or NULL*/, mbx_stream_t stream);
+
 /* ---------------------------------------------------------------- loss fwd+bwd (A7)
  * loss.py:88-101 given the matching: loc_loss = alpha * 1/2 sum (decoded-gt)^2 over
  * matched rows; conf_loss = -sum log(c_matched) - sum log(1 - c_unmatched + 1e-10),

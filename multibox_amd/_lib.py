@@ -35,6 +35,7 @@ _SIGS = {
     "mbx_decode_conf": (I, [P, P, P, I, I, F, P, P, P]),
     "mbx_match_workspace_bytes": (SZ, [I, I, I]),
     "mbx_match": (I, [P, P, P, P, F, I, I, I, P, P, P, SZ, P]),
+    "mbx_match_extend": (I, [P, P, P, P, F, I, I, I, P, P, P]),
     "mbx_loss_workspace_bytes": (SZ, [I]),
     "mbx_loss_fwd_bwd": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, P, SZ, P]),
     "mbx_loss_mined_workspace_bytes": (SZ, [I, I]),

@@ -69,3 +69,16 @@ def negative_mining(cfg):
         return None
     neg_per_pos = _int_key(cfg, "LOSS_NEG_PER_POS", 1)
     return neg_per_pos, (_int_key(cfg, "LOSS_MIN_NEG", 0) if cfg.get("LOSS_MIN_NEG") is not None else 0)
+
+
+def match_iou_threshold(cfg):
+    """Threshold matching behind the bipartite match (mbx_match_extend; not in the reference, so off when absent): None,
+    or LOSS_MATCH_IOU_THRESHOLD as a float in (0, 1] (absent or null = off).  Every prior the bipartite match left free
+    goes to the box it overlaps most if that IoU is over the key.  A bool, a string, a list, a NaN or a value outside
+    (0, 1] raises ValueError naming the key.  Host code only."""
+    v = cfg.get("LOSS_MATCH_IOU_THRESHOLD")
+    if v is None:
+        return None
+    if not (isinstance(v, (int, float)) and not isinstance(v, bool) and 0 < v <= 1):
+        raise ValueError("LOSS_MATCH_IOU_THRESHOLD must be a number in (0, 1], got %r" % (v,))
+    return float(v)

@@ -199,6 +199,69 @@ match_kernel(const float4* __restrict__ decoded, const float* __restrict__ conf,
   if (tid == 0) status[b] = 0;
 }
 
+// ------------------------------------------------------------- threshold matching
+// SSD's second matching step behind match_kernel (mbx_match_extend, mbx.h): every prior the bipartite match left free goes
+// to the box it overlaps most, if that IoU is over `thr`.  One workgroup per image, blockDim.x a multiple of 64 (P rounded
+// up, at most 1024).  The image's n boxes and their areas are widened to float64 into LDS once (40 B a box); a thread keeps
+// its prior's box and area in registers and walks the staged boxes, every lane reading the same LDS address (a broadcast).
+// The IoU is iou_corners' (boxes.h), term by term, with the prior as its first box; a pair that does not overlap has IoU 0,
+// which is never over a threshold > 0, so the float64 division is done for overlapping pairs only.  `best` starts at the
+// threshold and moves on a strictly larger IoU: the lowest j among the largest, and only where that is over the threshold.
+struct StagedBox { Box box; double area; };
+
+__global__ void __launch_bounds__(1024)
+match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict__ gt, const int* __restrict__ n_gt,
+                    const int* __restrict__ status, double thr, int P, int G, int* __restrict__ match,
+                    int* __restrict__ n_extra) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  StagedBox* boxes = reinterpret_cast<StagedBox*>(smem);      // [n]
+  __shared__ int added_waves[16];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = (int)blockDim.x;
+  const int n = n_gt[b];
+  if (status[b] != 0 || n <= 0 || n > G) {                    // skipped: the row stays as it is (n > G never has status 0)
+    if (tid == 0 && n_extra) n_extra[b] = 0;
+    return;
+  }
+  for (int j = tid; j < n; j += nt) {
+    const float4 q = gt[(size_t)b * G + j];
+    StagedBox s;
+    s.box = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    s.area = box_area(s.box);
+    boxes[j] = s;
+  }
+  __syncthreads();
+  int* mt = match + (size_t)b * P;
+  int added = 0;
+  for (int p = tid; p < P; p += nt) {
+    if (mt[p] >= 0) continue;                                 // mbx_match's choice stands
+    const float4 q = priors[p];
+    const Box e = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    const double area_e = box_area(e);
+    double best = thr;
+    int best_j = -1;
+    for (int j = 0; j < n; ++j) {
+      const Box g = boxes[j].box;
+      const double iw = fmin(e.x2, g.x2) - fmax(e.x1, g.x1), ih = fmin(e.y2, g.y2) - fmax(e.y1, g.y1);
+      if (iw > 0.0 && ih > 0.0) {
+        const double inter = iw * ih;
+        const double uni = area_e + boxes[j].area - inter;
+        const double iou = uni > 0.0 ? inter / uni : 0.0;
+        if (iou > best) { best = iou; best_j = j; }
+      }
+    }
+    if (best_j >= 0) { mt[p] = best_j; ++added; }
+  }
+  if (!n_extra) return;
+  added = wave_sum(added);
+  if ((tid & 63) == 0) added_waves[tid >> 6] = added;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int w = 0; w < (nt >> 6); ++w) total += added_waves[w];
+    n_extra[b] = total;
+  }
+}
+
 // ---------------------------------------------------------------------- loss
 __global__ void __launch_bounds__(kThreads)
 loss_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
@@ -490,6 +553,23 @@ extern "C" int mbx_match(const float* decoded, const float* conf, const float* g
   hipLaunchKernelGGL(match_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
                      reinterpret_cast<const float4*>(decoded), conf, reinterpret_cast<const float4*>(gt), n_gt,
                      alpha, P, G, match, status);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" int mbx_match_extend(const float* priors, const float* gt, const int32_t* n_gt, const int32_t* status,
+                                float iou_threshold, int B, int P, int G, int32_t* match, int32_t* n_extra,
+                                mbx_stream_t stream) {
+  if (!priors || !gt || !n_gt || !status || !match || B < 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (!(iou_threshold > 0.0f && iou_threshold <= 1.0f)) return MBX_ERR_INVALID_ARG;      // a NaN fails both
+  const size_t lds = (size_t)G * sizeof(StagedBox);
+  if (lds > 60 * 1024) return MBX_ERR_UNSUPPORTED;           // G > 1536: under the 64 KB a launch gets without asking
+  if (B == 0) return MBX_OK;
+  const int nthreads = P >= 1024 ? 1024 : (P + 63) / 64 * 64;
+  MBX_ENTER();
+  hipLaunchKernelGGL(match_extend_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
+                     reinterpret_cast<const float4*>(priors), reinterpret_cast<const float4*>(gt), n_gt, status,
+                     (double)iou_threshold, P, G, match, n_extra);
   MBX_LAUNCH_CHECK();
   return MBX_OK;
 }

@@ -42,6 +42,22 @@ def match_boxes(decoded, conf, gt_bboxes, num_gt_bboxes, alpha, match=None, stat
     return match, status
 
 
+def extend_matches(priors, gt_bboxes, num_gt_bboxes, status, match, iou_threshold, n_extra=None):
+    """mbx_match_extend (threshold matching, SSD section 2.2): priors [P,4] corners, gt [B,G,4], n [B], status [B] as
+    mbx_match left it, match int32 [B,P] updated IN PLACE -- every prior still unmatched goes to the box it overlaps
+    most if that IoU is over iou_threshold, in (0, 1].  n_extra int32 [B] (optional) receives the number added per image.
+    Returns (match, n_extra)."""
+    B, P = match.shape
+    G = gt_bboxes.shape[1]
+    assert priors.shape == (P, 4) and gt_bboxes.shape == (B, G, 4)
+    _lib.check(_lib.lib().mbx_match_extend(_f32(priors).data_ptr(), _f32(gt_bboxes).data_ptr(),
+                                           _i32(num_gt_bboxes).data_ptr(), _i32(status).data_ptr(), float(iou_threshold),
+                                           B, P, G, _i32(match).data_ptr(),
+                                           None if n_extra is None else _i32(n_extra).data_ptr(), _stream()),
+               "mbx_match_extend")
+    return match, n_extra
+
+
 def compute_assignments(locations, confidences, gt_bboxes, num_gt_bboxes, batch_size, alpha):
     """loss.py:8-53.  Same inputs/outputs as the py_func callback: returns
     [assignment_partitions int32 [B*P], stacked_gt_bboxes float32 [M,4]] (row order),
@@ -65,10 +81,15 @@ class MultiboxLoss:
 
     neg_per_pos (an int >= 1; None = off, the reference's loss): hard-negative mining -- per image only the
     max(min_neg, neg_per_pos * positives) highest-scoring negatives count (mbx_loss_fwd_bwd_mined, include/mbx.h);
-    their number per image is left in ``n_neg``.  What that does to AP on real data is not measured here."""
+    their number per image is left in ``n_neg``.  What that does to AP on real data is not measured here.
+
+    match_iou_threshold (a float in (0, 1]; None = off, the reference's bipartite match alone): threshold matching --
+    behind mbx_match every prior still free goes to the box it overlaps most if that IoU is over the threshold
+    (mbx_match_extend, include/mbx.h); the number added per image is left in ``n_extra``.  The loss, mined or not, reads
+    the extended ``match``.  What that does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
-                 min_neg=0):
+                 min_neg=0, match_iou_threshold=None):
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
         self.P = self.priors.shape[0]
         self.B, self.G, self.alpha = int(batch_size), int(max_num_bboxes), float(location_loss_alpha)
@@ -86,6 +107,12 @@ class MultiboxLoss:
             self.n_neg = torch.zeros((self.B,), dtype=torch.int32, device=device)
             ws_bytes = _lib.lib().mbx_loss_mined_workspace_bytes(self.B, self.P)
         self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+        self.match_iou_threshold, self.n_extra = match_iou_threshold, None
+        if match_iou_threshold is not None:
+            if not 0.0 < float(match_iou_threshold) <= 1.0:
+                raise ValueError("match_iou_threshold must be in (0, 1], got %r" % (match_iou_threshold,))
+            self.match_iou_threshold = float(match_iou_threshold)
+            self.n_extra = torch.zeros((self.B,), dtype=torch.int32, device=device)
 
     def forward_backward(self, raw_locs, logits, gt_bboxes, num_gt_bboxes, grad_scale=1.0, conf_is_logit=True):
         """raw_locs [B,P,4], logits [B,P] f32 -> (loss2 [2] = {location_loss, confidence_loss}, d_locs, d_logits)."""
@@ -103,6 +130,10 @@ class MultiboxLoss:
         _lib.check(l.mbx_match(self.decoded.data_ptr(), self.conf.data_ptr(), _f32(gt_bboxes).data_ptr(),
                                _i32(num_gt_bboxes).data_ptr(), self.alpha, B, P, G, self.match.data_ptr(),
                                self.status.data_ptr(), None, 0, s), "mbx_match")
+        if self.match_iou_threshold is not None:
+            _lib.check(l.mbx_match_extend(self.priors.data_ptr(), gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),
+                                          self.status.data_ptr(), self.match_iou_threshold, B, P, G,
+                                          self.match.data_ptr(), self.n_extra.data_ptr(), s), "mbx_match_extend")
         if self.neg_per_pos is None:
             _lib.check(l.mbx_loss_fwd_bwd(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
                                           gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),

@@ -40,13 +40,15 @@ class Trainer:
     def __init__(self, net: Net, bbox_priors, max_num_bboxes=13, location_loss_alpha=1000.0, initial_learning_rate=0.01,
                  decay_steps_=7116, learning_rate_decay_factor=0.94, staircase=True, rmsprop_decay=0.9,
                  rmsprop_momentum=0.0, rmsprop_epsilon=1.0, moving_average_decay=0.9999, use_graph=True,
-                 n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0):
+                 n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
+                 match_iou_threshold=None):
         assert net.mode == "train"
         self.net = net
         self.pg = process_group
         # neg_per_pos / min_neg: hard-negative mining of the confidence loss (MultiboxLoss; None = the reference's loss)
+        # match_iou_threshold: threshold matching behind the bipartite match (MultiboxLoss; None = the reference's match alone)
         self.loss = MultiboxLoss(bbox_priors, net.B, max_num_bboxes, location_loss_alpha, device=net.dev,
-                                 neg_per_pos=neg_per_pos, min_neg=min_neg)
+                                 neg_per_pos=neg_per_pos, min_neg=min_neg, match_iou_threshold=match_iou_threshold)
         assert self.loss.P == net.P, "priors (%d) do not match the network's predictions (%d)" % (self.loss.P, net.P)
         self.loss.d_locs, self.loss.d_logits = net.d_locs, net.d_logits
         self.lr0, self.dsteps, self.lr_factor, self.staircase = initial_learning_rate, decay_steps_, learning_rate_decay_factor, staircase
@@ -555,3 +557,8 @@ class Trainer:
         """Mean over the batch of the negatives the last step's confidence loss kept, or None without hard-negative
         mining -- host sync; call it at logging intervals."""
         return None if self.loss.n_neg is None else float(self.loss.n_neg.float().mean())
+
+    def extra_matches_per_image(self):
+        """Mean over the batch of the priors threshold matching added to the last step's bipartite match, or None without
+        it -- host sync; call it at logging intervals."""
+        return None if self.loss.n_extra is None else float(self.loss.n_extra.float().mean())

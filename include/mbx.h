@@ -66,7 +66,13 @@ int mbx_decode_conf(const float* raw_locs /*[B,P,4]*/, const float* logits /*[B,
  * assignment in float64 (shortest augmenting path; scipy's linear_sum_assignment,
  * loss.py:40).  match[b,p] = gt index or -1; the reference's 0/1 partition and
  * row-ordered stacked_gt (loss.py:44-48) follow from it.
- * status[b]: 0 ok, 1 n_gt > P (infeasible), 2 non-finite cost (scipy raises there).    */
+ * status[b]: 0 ok, 1 n_gt > P or n_gt > G (infeasible), 2 a non-finite location or log-confidence, or no assignment of
+ * finite cost (scipy raises there); n_gt <= 0: status 0, nothing matched.  Where status[b] != 0 the row of `match` is all -1.
+ * Rows j >= n_gt[b] of `gt` are padding and never read.  A cost that overflows float32 to +inf is a legal entry, as for scipy.
+ * Among assignments of equal total cost the choice is the kernel's own (shortest augmenting path; among equal candidates
+ * a free prediction first, then the lowest index) and may differ from scipy's; it is the same on every call and does not
+ * depend on B or on the image's place in the launch.  P and G are limited by 36 P + 16 G + 16 <= 150 KiB of LDS (P = 4221
+ * at G = 100), above: MBX_ERR_UNSUPPORTED, nothing launched or written.                                                */
 size_t mbx_match_workspace_bytes(int B, int P, int G);
 int mbx_match(const float* decoded /*[B,P,4]*/, const float* conf /*[B,P]*/,
               const float* gt /*[B,G,4]*/, const int32_t* n_gt /*[B]*/, float alpha,
@@ -160,7 +166,10 @@ int mbx_loss_fwd_bwd_mined(const float* decoded /*[B,P,4]*/, const float* conf_i
  * float64 incl. the flip (106-131).  Ties in confidence: higher prediction index first
  * (the reference's order among ties is undefined).  `conf` may hold ANY float (the sort key is an order-
  * preserving image of the float bits): negative values, values >= 1 and infinities order as numpy's
- * argsort does; a NaN sorts first, as argsort(...)[::-1] (detect.py:423) places it.            */
+ * argsort does; a NaN sorts first, as argsort(...)[::-1] (detect.py:423) places it.
+ * A NaN COORDINATE is clipped to 0 (fminf(fmaxf(x, 0), 1)) and filtered and reported as 0; numpy's clip keeps the NaN, which
+ * then passes the reference's strict filter.  out_count[b] = clamp(min(kept, max_to_keep), 0, k_max); the slots at or past it
+ * are 0.0 / 0.0f / -1.  P <= 16384, above: MBX_ERR_UNSUPPORTED, nothing launched or written.                          */
 typedef struct {
   int32_t offset_y, offset_x; /* batched_offsets  (detect.py:190-281) */
   int32_t patch_h, patch_w;   /* batched_dims */
@@ -180,7 +189,9 @@ int mbx_decode_filter_topk(const float* raw_locs /*[B,P,4]*/, const float* conf 
  * north_star names an NMS stage; the reference has none -- detect.py:408-443 keeps the top max_to_keep boxes -- so it is
  * off by default and outside the parity path).  Boxes are taken in their stored (score-descending) order; box i is
  * dropped iff IoU(i, j) > iou_threshold for an earlier KEPT box j; survivors are compacted to the front of each row of
- * out_boxes / out_scores / out_index and out_count[b] becomes their number.  IoU in float64, k_max <= 1024.      */
+ * out_boxes / out_scores / out_index and out_count[b] becomes their number.  IoU in float64, k_max <= 1024 (above:
+ * MBX_ERR_UNSUPPORTED, nothing launched or written).  count[b] is clamped to [0, k_max] on the way in; the slots at or
+ * past the new count keep what they held.                                                                             */
 int mbx_nms(double* boxes /*[B,k_max,4] x1,y1,x2,y2*/, float* scores /*[B,k_max]*/, int32_t* index /*[B,k_max]*/,
             int32_t* count /*[B], in/out*/, int B, int k_max, double iou_threshold, mbx_stream_t stream);
 

@@ -629,7 +629,7 @@ nms_kernel(double* __restrict__ boxes, float* __restrict__ scores, int32_t* __re
            int32_t* __restrict__ count, int k_max, double thr) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long nms_lds[];
   const int b = blockIdx.x;
-  const int K = min(count[b], k_max);
+  const int K = max(min(count[b], k_max), 0);                // (a count <= -64 made W negative and K * W a positive trip count)
   const int W = (K + 63) >> 6;                               // 64-bit words per row
   unsigned long long* rows = nms_lds;                        // [K][W]
   unsigned long long* removed = nms_lds + (size_t)K * W;     // [W]

@@ -64,17 +64,25 @@ class ConvOp:
         self.Cin = x.C
         self.M = out.M
         self.name = members[0].scope if len(members) == 1 else "+".join(m.scope for m in members)
+        self.group = None           # its BnUnit if that has several members (Net.group_bn), else None
+        self.unit = None            # the BnUnit of a training-mode batch-norm convolution (Net._alloc_scratch)
+        self.fused_pool = None      # the max-pool whose backward rides in this layer's batch-norm backward (Net._pool_producer)
+        self.relu_bits = None       # residual: the sign bits of its output, where a data gradient reads them as its relu mask
+        self.fdesc = None           # its data gradient with the batch-norm backward of its input's units as the tail
+        self.head_grad = None       # head: bf16 gradient of its output
 
     # offsets into the flat parameter buffers are assigned by Net.finalize()
     w_off = b_off = beta_off = dw_off = -1
 
 
-class BnGroup:
-    """Sibling convolutions normalised by ONE finalize / apply / backward launch (mbx.h, BATCH-NORM GROUPS): their pre-BN
-    outputs (and gradients) are channel slices of one contiguous [M, K] tensor, member i at channels koff[i]."""
+class BnUnit:
+    """What ONE finalize / apply / backward launch normalises: a batch-norm convolution, or sibling convolutions declared a
+    group (mbx.h, BATCH-NORM GROUPS).  The pre-BN outputs (and gradients) of the members are channel slices of one contiguous
+    [M, K] tensor, y (dy), member i at channels koff[i]; the statistics, betas and workspaces of the unit start at its lead's."""
 
     def __init__(self, members):
         self.members = list(members)
+        self.lead = self.members[0]
         self.K = sum(m.K for m in members)
         self.koff, k = [], 0
         for m in members:
@@ -82,7 +90,7 @@ class BnGroup:
             k += m.K
         self.y = self.dy = None
         self.fwd_desc, self.dgrad_desc = {}, {}   # member index -> its forward / data-gradient descriptor
-        self.pair_fwd = self.pair_bwd = False     # a group of TWO: both convolutions in one launch (mbx_conv_pair), if it applies
+        self.pair_fwd = self.pair_bwd = False     # a unit of TWO: both convolutions in one launch (mbx_conv_pair), if it applies
         self.rows = [0] * len(members)          # statistics partial rows of each member's convolution (tile height)
         self.stats_off = [0] * len(members)     # float offsets of the members' partial rows in Net.stats_scratch
 
@@ -95,6 +103,94 @@ class BnGroup:
         for i, (ko, r) in enumerate(zip(self.koff, rel)):
             m.c_begin[i], m.offset[i] = ko, r - base
         return base, m
+
+    def target(self, views):
+        """(address, pixel stride, mbx_chan_map or None) of the members' activations (gradients) `views`, as the mapped
+        batch-norm launches take them: a unit of one passes its own view and NO map."""
+        if len(views) == 1:
+            return views[0].ptr, views[0].ld, None
+        assert all(v.buf is views[0].buf and v.ld == views[0].ld for v in views)
+        base, m = self.chan_map(views)
+        return views[0].buf.data_ptr() + 2 * base, views[0].ld, m
+
+
+def dgrad_probe(X):
+    """Geometry of convolution X's data gradient (the fields the ops.*_applies rules look at; no addresses)."""
+    dd = ops.ConvDesc()
+    dd.R, dd.S, dd.stride, dd.epilogue, dd.C_in, dd.C_out = X.R, X.S, 1, ops.EPI_STORE, X.K, X.Cin
+    dd.N, dd.H_in, dd.W_in, dd.H_out, dd.W_out = X.x.N, X.out.H, X.out.W, X.x.H, X.x.W
+    dd.rscale = X.rscale if X.kind == "residual" else 0.0
+    return dd
+
+
+def plan_consumer_fusion(convs, fwd, unit_ok, consumer_ok, align):
+    """Which batch-norm units can hand (part of) their backward to the data gradients that write their activation gradient,
+    and which data gradients take it.  A consumer convolution X is CONVERTIBLE when it is a trainable stride-1 convolution
+    with a data gradient whose input view is tiled exactly by outputs of eligible units' members (at most 4 segments, each
+    starting at a multiple of `align` channels), nothing else reads those channels and consumer_ok(X); a unit (trainable,
+    at most 2048 channels, unit_ok(unit)) is ELIGIBLE when every channel of every member has exactly one consumer and that
+    one is convertible.  Fixed point of the two.  `convs`: the convolutions, `fwd`: every forward op (pools read tensors too).
+    Returns (eligible units, {X: [(first channel relative to X's input view, member, first channel inside the member's
+    output, channels)]}), both in forward order.  Touches no device and no environment."""
+    is_conv = set(id(c) for c in convs)
+    units = [op.unit for op in convs if op.kind == "bn" and op.trainable and op is op.unit.lead and op.unit.K <= 2048
+             and unit_ok(op.unit)]
+
+    def member_at(buf, c):
+        for u in units:
+            for m in u.members:
+                if m.out.buf is buf and m.out.ch_off <= c < m.out.ch_off + m.K:
+                    return m
+        return None
+
+    def readers(buf, lo, hi):
+        """forward ops that read channels [lo, hi) of buf: as their input, or as a residual block's skip (trunk) tensor"""
+        r = [o for o in fwd if o.x.buf is buf and o.x.ch_off < hi and o.x.ch_off + o.x.C > lo]
+        r += [o for o in fwd if id(o) in is_conv and o.skip is not None and o.skip.buf is buf and
+              o.skip.ch_off < hi and o.skip.ch_off + o.skip.C > lo]
+        return r
+
+    def segments(X):
+        """tiling of X's input view by batch-norm member outputs, or None"""
+        segs, c, end = [], X.x.ch_off, X.x.ch_off + X.x.C
+        while c < end:
+            m = member_at(X.x.buf, c)
+            if m is None:
+                return None
+            n = min(end, m.out.ch_off + m.K) - c
+            segs.append((c - X.x.ch_off, m, c - m.out.ch_off, n))
+            c += n
+        if len(segs) > 4 or any(sg[0] % align for sg in segs):
+            return None
+        return segs
+
+    eligible = set(id(u) for u in units)
+    while True:
+        conv_ok = {}
+        for X in fwd:
+            if id(X) not in is_conv or not X.need_dx or not X.trainable or X.stride != 1:
+                continue
+            segs = segments(X)
+            if segs is None or any(id(sg[1].unit) not in eligible for sg in segs):
+                continue
+            if len(readers(X.x.buf, X.x.ch_off, X.x.ch_off + X.x.C)) != 1:
+                continue                                   # someone else reads (part of) these channels: accumulated gradient
+            if consumer_ok(X):
+                conv_ok[id(X)] = (X, segs)
+        drop = set()
+        for u in units:
+            if id(u) not in eligible:
+                continue
+            for m in u.members:
+                rd = readers(m.out.buf, m.out.ch_off, m.out.ch_off + m.K)
+                covered = sorted((max(o.x.ch_off, m.out.ch_off), min(o.x.ch_off + o.x.C, m.out.ch_off + m.K)) for o in rd)
+                tiled = bool(covered) and covered[0][0] == m.out.ch_off and covered[-1][1] == m.out.ch_off + m.K and \
+                    all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
+                if not tiled or any(id(o) not in conv_ok for o in rd):
+                    drop.add(id(u))
+        if not drop:
+            return [u for u in units if id(u) in eligible], dict(conv_ok.values())
+        eligible -= drop
 
 
 class Net:
@@ -185,6 +281,7 @@ class Net:
         self.written = set()       # gradient regions already written in the backward pass (build time)
         self.heads = []
         self._bufs = []
+        self._keep = []            # ctypes tables and workspaces the pre-bound launches point into
         self._build()
         self._finalize(seed)
 
@@ -534,103 +631,82 @@ class Net:
 
     def _alloc_scratch(self):
         dev = self.dev
-        max_y = max_stats = max_bwd = n_stats16 = 0
-        self.y_tmp = {}
+        max_stats = max_bwd = n_stats16 = 0
         l = _lib.lib()
         # batch-norm groups that apply: training-mode BN on every member, same pixels / relu / trainability, consecutive in
         # forward order, outputs in ONE buffer, betas contiguous, the group small enough for the lane-owns-a-channel-group kernels
-        for op in self.convs:
-            op.group = None
         for members in self._bn_group_requests:
             idx = [self.fwd.index(m) for m in members]
             ok = all(m.kind == "bn" and m.M == members[0].M and m.relu == members[0].relu and m.trainable == members[0].trainable and
                      m.out.buf is members[0].out.buf and m.out.ld == members[0].out.ld and m.K % 8 == 0 for m in members)
             ok = ok and idx == list(range(idx[0], idx[0] + len(idx))) and len(members) <= 4
             ok = ok and all(b.beta_off == a.beta_off + a.K for a, b in zip(members, members[1:]))
-            g = BnGroup(members)
+            g = BnUnit(members)
             ok = ok and g.K <= 2048 and g.chan_map([m.out for m in members])[0] >= 0
             if ok:
                 self.bn_groups.append(g)
                 for m in members:
-                    m.group = g
+                    m.group = m.unit = g
         for op in self.convs:
             if op.kind == "bn":
-                g = op.group
-                lead = g is None or op is g.members[0]
-                K_all = op.K if g is None else g.K
+                u = op.unit = op.unit or BnUnit([op])          # every other batch-norm convolution: a unit of one
+                i = u.members.index(op)
                 N_, H_, W_ = op.out.N, op.out.H, op.out.W
-                if lead:
-                    ybuf = torch.empty((op.M, K_all), dtype=torch.bfloat16, device=dev)      # pre-BN output, kept for backward
-                    self._bufs.append(ybuf)
-                    if g is not None:
-                        g.y = ybuf
-                else:
-                    ybuf = g.y
-                ko = 0 if g is None else g.koff[g.members.index(op)]
-                op.y_view = View(ybuf, N_, H_, W_, op.K, K_all, ko)
-                if lead:
-                    op.stats16_base = n_stats16                 # [STATS_ROWS][K_all][2] int64 (fixed point) of the layer / group, in float units
-                    n_stats16 += STATS_ROWS * K_all * 4
-                op.stats16_off = (op.stats16_base if g is None else g.members[0].stats16_base) + 4 * ko
+                if op is u.lead:
+                    u.y = torch.empty((op.M, u.K), dtype=torch.bfloat16, device=dev)      # pre-BN output, kept for backward
+                    self._bufs.append(u.y)
+                    u.stats16_base = n_stats16                  # [STATS_ROWS][K][2] int64 (fixed point) of the unit, in float units
+                    n_stats16 += STATS_ROWS * u.K * 4
+                op.y_view = View(u.y, N_, H_, W_, op.K, u.K, u.koff[i])
+                op.stats16_off = u.stats16_base + 4 * u.koff[i]
                 d = self._desc(op, op.y_view)
                 rows = max(ops.conv_stats_rows(d), (op.M + 63) // 64)                                   # any tile height
-                if g is None and ops.splitk_slices(d, self.n_cus):
+                if len(u.members) == 1 and ops.splitk_slices(d, self.n_cus):
                     rows = max(rows, (op.M + 15) // 16)                                                   # split-K: a row per 16 pixels
-                if g is None:
-                    op.stats_off = 0
-                    max_stats = max(max_stats, rows * op.K * 2)
-                else:
-                    i = g.members.index(op)
-                    g.stats_off[i] = 0 if i == 0 else g.stats_off[i - 1] + g._bound
-                    g._bound = rows * op.K * 2
-                    op.stats_off = g.stats_off[i]
-                    max_stats = max(max_stats, op.stats_off + g._bound)
+                op.stats_off = u.stats_off[i] = 0 if i == 0 else u.stats_end      # the members' partial rows, one after the other
+                u.stats_end = op.stats_off + rows * op.K * 2
+                max_stats = max(max_stats, u.stats_end)
                 if op.trainable:
                     # dy of EVERY layer stays alive until the grouped weight-gradient launch at the end of its backward
                     # segment (3.2 GB at BATCH_SIZE 64: sized for 288 GB of HBM, not for reuse)
-                    if lead:
-                        dybuf = torch.empty((op.M, K_all), dtype=torch.bfloat16, device=dev)
-                        self._bufs.append(dybuf)
-                        if g is not None:
-                            g.dy = dybuf
-                        max_bwd = max(max_bwd, l.mbx_bn_bwd_rows(op.M, K_all) * K_all * 2,
-                                      l.mbx_bn_bwd_rows_pooled(N_, H_, W_, K_all) * K_all * 2)       # (either form of the three-launch backward)
-                    else:
-                        dybuf = g.dy
-                    op.dy_view = View(dybuf, N_, H_, W_, op.K, K_all, ko)
-        # one-launch BN backward: per-layer (per-group) accumulators + arrival counter, zeroed with the gradients every step
+                    if op is u.lead:
+                        u.dy = torch.empty((op.M, u.K), dtype=torch.bfloat16, device=dev)
+                        self._bufs.append(u.dy)
+                        max_bwd = max(max_bwd, l.mbx_bn_bwd_rows(op.M, u.K) * u.K * 2,
+                                      l.mbx_bn_bwd_rows_pooled(N_, H_, W_, u.K) * u.K * 2)       # (either form of the three-launch backward)
+                    op.dy_view = View(u.dy, N_, H_, W_, op.K, u.K, u.koff[i])
+        # one-launch BN backward: per-unit accumulators + arrival counter, zeroed with the gradients every step
         ws_floats = 0
         for op in self.convs:
             op.bn_ws_off = -1
-            g = getattr(op, "group", None)
-            if g is not None and op is not g.members[0]:
-                op.bn_ws_off = g.members[0].bn_ws_off
+            if op.kind != "bn":
                 continue
-            K_all = op.K if g is None else g.K
-            if op.kind == "bn" and op.trainable and torch.device(dev).type == "cuda" and l.mbx_bn_bwd_onepass_supported(op.M, K_all, self.chain_cap or self.bn_max_wg):
+            u = op.unit
+            if op is not u.lead:
+                op.bn_ws_off = u.lead.bn_ws_off
+            elif op.trainable and torch.device(dev).type == "cuda" and l.mbx_bn_bwd_onepass_supported(op.M, u.K, self.chain_cap or self.bn_max_wg):
                 op.bn_ws_off = ws_floats
-                ws_floats += (l.mbx_bn_bwd_onepass_workspace_bytes(K_all) // 4 + 7) // 8 * 8
+                ws_floats += (l.mbx_bn_bwd_onepass_workspace_bytes(u.K) // 4 + 7) // 8 * 8
         self._plan_bw_stats()
         for op in self.convs:
             op.bw_rows_off = -1
-            u = getattr(op, "bw_unit", None)
+            u = op.bw_unit
             if u is not None:
-                lead = u[0]
-                if op is lead:
-                    op.bw_rows_off = ws_floats                       # [STATS_ROWS][K_all][2], cleared with the workspace every step
-                    ws_floats += STATS_ROWS * sum(m.K for m in u) * 2
+                if op is u.lead:
+                    op.bw_rows_off = ws_floats                       # [STATS_ROWS][K][2], cleared with the workspace every step
+                    ws_floats += STATS_ROWS * u.K * 2
                 else:
-                    op.bw_rows_off = lead.bw_rows_off
+                    op.bw_rows_off = u.lead.bw_rows_off
         # fused data-gradient + BN-backward launches: accumulators per batch-norm unit, a grid-barrier control block per launch
         self._plan_fused_bwd()
         for op in self.convs:
             op.fb_acc_off = op.fb_bar_off = -1
         for op in self.convs:
             u = op.fb_unit
-            if u is not None and op is u[0]:
+            if u is not None and op is u.lead:
                 ws_floats = (ws_floats + 31) // 32 * 32
                 op.fb_acc_off = ws_floats
-                ws_floats += ops.BN_BWD_SLOTS * 2 * sum(m.K for m in u)
+                ws_floats += ops.BN_BWD_SLOTS * 2 * u.K
             if op.fb_segments is not None:
                 ws_floats = (ws_floats + 31) // 32 * 32
                 op.fb_bar_off = ws_floats
@@ -659,236 +735,95 @@ class Net:
         self.reg_loss = torch.zeros(1, dtype=torch.float32, device=dev)
 
     def _plan_bw_stats(self):
-        """Which batch-norm layers (groups) get their backward statistics from the data gradient(s) that write their
-        activation gradient, and which data gradients carry the statistics epilogue.  A consumer convolution X is CONVERTIBLE
-        when it is a trainable stride-1 convolution with a data gradient whose input view is tiled exactly by outputs of
-        eligible batch-norm members (segments at multiples of 32 channels, at most 4) and nothing else reads those channels;
-        a unit is ELIGIBLE when every channel of every member has exactly one consumer and that one is convertible.  Fixed point
-        of the two.  Sets op.bw_unit (tuple of the unit's members) on eligible layers and op.bw_segments on convertible consumers:
-        [(first channel relative to X's input view, member, first channel inside the member's output, channels)]."""
+        """Which batch-norm units get their backward statistics from the data gradient(s) that write their activation
+        gradient, and which data gradients carry the statistics epilogue (plan_consumer_fusion: segments at multiples of 32
+        channels; consumers whose data gradient is a direct or resident-image launch have no such epilogue -- the stem's
+        layers stay on the grid-barrier form).  Sets op.bw_unit (its unit) on the members of eligible units and
+        op.bw_segments on convertible consumers."""
         for op in self.convs:
             op.bw_unit, op.bw_segments = None, None
         if not self.bw_stats or torch.device(self.dev).type != "cuda":
             return
-        units = []
-        for op in self.convs:
-            if op.kind != "bn" or not op.trainable:
-                continue
-            g = op.group
-            if g is not None and op is not g.members[0]:
-                continue
-            mem = tuple([op] if g is None else g.members)
-            if sum(m.K for m in mem) <= 2048:
-                units.append(mem)
-        unit_of = {id(m): u for u in units for m in u}
 
-        def member_at(buf, c):
-            for u in units:
-                for m in u:
-                    if m.out.buf is buf and m.out.ch_off <= c < m.out.ch_off + m.K:
-                        return m
-            return None
+        def consumer_ok(X):
+            dd = dgrad_probe(X)
+            return not (ops.direct3_applies(dd) or ops.directw_applies(dd) or ops.resident_applies(dd))
 
-        def readers(buf, lo, hi):
-            """forward ops that read channels [lo, hi) of buf: as their input, or as a residual block's skip (trunk) tensor"""
-            r = [o for o in self.fwd if o.x.buf is buf and o.x.ch_off < hi and o.x.ch_off + o.x.C > lo]
-            r += [o for o in self.fwd if isinstance(o, ConvOp) and o.skip is not None and o.skip.buf is buf and
-                  o.skip.ch_off < hi and o.skip.ch_off + o.skip.C > lo]
-            return r
-
-        def segments(X):
-            """tiling of X's input view by batch-norm member outputs, or None"""
-            segs, c, end = [], X.x.ch_off, X.x.ch_off + X.x.C
-            while c < end:
-                m = member_at(X.x.buf, c)
-                if m is None:
-                    return None
-                n = min(end, m.out.ch_off + m.K) - c
-                segs.append((c - X.x.ch_off, m, c - m.out.ch_off, n))
-                c += n
-            if len(segs) > 4 or any(sg[0] % 32 for sg in segs):
-                return None
-            return segs
-
-        eligible = set(id(u) for u in units)
-        while True:
-            conv_ok = {}
-            for X in self.fwd:
-                if not isinstance(X, ConvOp) or not X.need_dx or not X.trainable or X.stride != 1:
-                    continue
-                segs = segments(X)
-                if segs is None or any(id(unit_of[id(sg[1])]) not in eligible for sg in segs):
-                    continue
-                if len(readers(X.x.buf, X.x.ch_off, X.x.ch_off + X.x.C)) != 1:
-                    continue                                   # someone else reads (part of) these channels: accumulated gradient
-                # (the direct 3x3 launch has no statistics epilogue: the stem's layers stay on the grid-barrier form)
-                dd = ops.ConvDesc()                               # (the fields ops.direct3_applies looks at, of X's data gradient)
-                dd.R, dd.S, dd.stride, dd.epilogue, dd.C_in, dd.C_out = X.R, X.S, 1, ops.EPI_STORE, X.K, X.Cin
-                dd.N, dd.H_out, dd.W_out, dd.rscale = X.x.N, X.x.H, X.x.W, (X.rscale if X.kind == "residual" else 0.0)
-                dd.W_out = X.x.W
-                dd.H_in, dd.W_in, dd.H_out = X.x.H, X.x.W, X.x.H
-                if ops.direct3_applies(dd) or ops.directw_applies(dd) or (X.out.H == X.x.H and X.out.W == X.x.W and ops.resident_applies(dd)):
-                    continue
-                conv_ok[id(X)] = segs
-            drop = set()
-            for u in units:
-                if id(u) not in eligible:
-                    continue
-                for m in u:
-                    rd = readers(m.out.buf, m.out.ch_off, m.out.ch_off + m.K)
-                    covered = sorted((max(o.x.ch_off, m.out.ch_off), min(o.x.ch_off + o.x.C, m.out.ch_off + m.K)) for o in rd)
-                    tiled = bool(covered) and covered[0][0] == m.out.ch_off and covered[-1][1] == m.out.ch_off + m.K and \
-                        all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
-                    if not tiled or any(id(o) not in conv_ok for o in rd):
-                        drop.add(id(u))
-            if not drop:
-                break
-            eligible -= drop
+        units, segs = plan_consumer_fusion(self.convs, self.fwd, lambda u: True, consumer_ok, align=32)
         for u in units:
-            if id(u) in eligible:
-                for m in u:
-                    m.bw_unit = u
-        for X in self.fwd:
-            if isinstance(X, ConvOp) and id(X) in conv_ok:
-                X.bw_segments = conv_ok[id(X)]
+            for m in u.members:
+                m.bw_unit = u
+        for X, sg in segs.items():
+            X.bw_segments = sg
 
     def _plan_fused_bwd(self):
-        """Which batch-norm layers (groups) have their backward run by the data gradient(s) that write their activation
-        gradient (mbx_conv_desc.bn_bwd), and which data gradients carry that tail.  A consumer convolution X is CONVERTIBLE
-        when it is a trainable stride-1 convolution with a data gradient whose input view is tiled exactly by outputs of
-        eligible batch-norm members (segments at multiples of 8 channels, at most 4), nothing else reads those channels,
-        and its data gradient is not one of the stem's direct launches; a unit is ELIGIBLE when every channel of every
-        member has exactly one consumer and that one is convertible.  Fixed point of the two.  Sets op.fb_unit (tuple of the
-        unit's members) on eligible layers and op.fb_segments on convertible consumers:
-        [(first channel relative to X's input view, member, first channel inside the member's output, channels)]."""
+        """Which batch-norm units have their backward run by the data gradient(s) that write their activation gradient
+        (mbx_conv_desc.bn_bwd), and which data gradients carry that tail (plan_consumer_fusion: segments at multiples of 8
+        channels; not a consumer whose data gradient is one of the stem's direct launches, or whose tail would walk more
+        than one round of tiles).  Sets op.fb_unit (its unit) on the members of eligible units and op.fb_segments on
+        convertible consumers."""
         for op in self.convs:
             op.fb_unit, op.fb_segments = None, None
         if not self.fuse_bwd:
             return
-        units = []
-        for op in self.convs:
-            if op.kind != "bn" or not op.trainable:
-                continue
-            g = op.group
-            if g is not None and op is not g.members[0]:
-                continue
-            mem = tuple([op] if g is None else g.members)
-            if sum(m.K for m in mem) <= 2048 and all(getattr(m, "fused_pool", None) is None for m in mem):
-                units.append(mem)
-        unit_of = {id(m): u for u in units for m in u}
         pairs_ok = os.environ.get("MBX_FUSE_BWD_PAIRS", "1") != "0"
         only = re.compile(os.environ["MBX_FUSE_BWD_ONLY"]) if os.environ.get("MBX_FUSE_BWD_ONLY") else None   # consumers by name (A/B)
+        max_rounds = int(os.environ.get("MBX_FUSE_BWD_MAX_ROUNDS", "1"))
 
-        def member_at(buf, c):
-            for u in units:
-                for m in u:
-                    if m.out.buf is buf and m.out.ch_off <= c < m.out.ch_off + m.K:
-                        return m
-            return None
+        def consumer_ok(X):
+            if X.x.img_stride != X.x.H * X.x.W * X.x.ld or X.Cin % 8 or (only is not None and not only.search(X.name)):
+                return False
+            if not pairs_ok and X.kind == "bn" and len(X.unit.members) == 2:
+                return False
+            dd = dgrad_probe(X)
+            if ops.direct3_applies(dd):
+                return False                               # (the stem: the direct launch has no tail; its layers keep their own backward)
+            # a tail walks its workgroup's tiles one after the other: on one tile it costs what the BN-backward launch costs, on
+            # several it costs more (block35 at BATCH_SIZE 64: 5 tails of 15-40 us for 3 launches of 17 us, +0.37 ms per step)
+            return ops.fused_tail_rounds(dd, self.n_cus) <= max_rounds
 
-        def readers(buf, lo, hi):
-            r = [o for o in self.fwd if o.x.buf is buf and o.x.ch_off < hi and o.x.ch_off + o.x.C > lo]
-            r += [o for o in self.fwd if isinstance(o, ConvOp) and o.skip is not None and o.skip.buf is buf and
-                  o.skip.ch_off < hi and o.skip.ch_off + o.skip.C > lo]
-            return r
-
-        def segments(X):
-            segs, c, end = [], X.x.ch_off, X.x.ch_off + X.x.C
-            while c < end:
-                m = member_at(X.x.buf, c)
-                if m is None:
-                    return None
-                n = min(end, m.out.ch_off + m.K) - c
-                segs.append((c - X.x.ch_off, m, c - m.out.ch_off, n))
-                c += n
-            if len(segs) > 4 or any(sg[0] % 8 for sg in segs):
-                return None
-            return segs
-
-        eligible = set(id(u) for u in units)
-        conv_ok = {}
-        while True:
-            conv_ok = {}
-            for X in self.fwd:
-                if not isinstance(X, ConvOp) or not X.need_dx or not X.trainable or X.stride != 1:
-                    continue
-                if X.x.img_stride != X.x.H * X.x.W * X.x.ld or X.Cin % 8 or (only is not None and not only.search(X.name)):
-                    continue
-                if not pairs_ok and X.kind == "bn" and X.group is not None and len(X.group.members) == 2:
-                    continue
-                segs = segments(X)
-                if segs is None or any(id(unit_of[id(sg[1])]) not in eligible for sg in segs):
-                    continue
-                if len(readers(X.x.buf, X.x.ch_off, X.x.ch_off + X.x.C)) != 1:
-                    continue                                   # someone else reads (part of) these channels: accumulated gradient
-                dd = ops.ConvDesc()                               # (the fields ops.direct3_applies looks at, of X's data gradient)
-                dd.R, dd.S, dd.stride, dd.epilogue, dd.C_in, dd.C_out = X.R, X.S, 1, ops.EPI_STORE, X.K, X.Cin
-                dd.N, dd.H_in, dd.W_in, dd.H_out, dd.W_out = X.x.N, X.out.H, X.out.W, X.x.H, X.x.W
-                if ops.direct3_applies(dd):
-                    continue                                   # (the stem: the direct launch has no tail; its layers keep their own backward)
-                # a tail walks its workgroup's tiles one after the other: on one tile it costs what the BN-backward launch costs, on
-                # several it costs more (block35 at BATCH_SIZE 64: 5 tails of 15-40 us for 3 launches of 17 us, +0.37 ms per step)
-                if ops.fused_tail_rounds(dd, self.n_cus) > int(os.environ.get("MBX_FUSE_BWD_MAX_ROUNDS", "1")):
-                    continue
-                conv_ok[id(X)] = segs
-            drop = set()
-            for u in units:
-                if id(u) not in eligible:
-                    continue
-                for m in u:
-                    rd = readers(m.out.buf, m.out.ch_off, m.out.ch_off + m.K)
-                    covered = sorted((max(o.x.ch_off, m.out.ch_off), min(o.x.ch_off + o.x.C, m.out.ch_off + m.K)) for o in rd)
-                    tiled = bool(covered) and covered[0][0] == m.out.ch_off and covered[-1][1] == m.out.ch_off + m.K and \
-                        all(a[1] == b[0] for a, b in zip(covered, covered[1:]))
-                    if not tiled or any(id(o) not in conv_ok for o in rd):
-                        drop.add(id(u))
-            if not drop:
-                break
-            eligible -= drop
+        units, segs = plan_consumer_fusion(self.convs, self.fwd, lambda u: all(m.fused_pool is None for m in u.members),
+                                           consumer_ok, align=8)
         for u in units:
-            if id(u) in eligible:
-                for m in u:
-                    m.fb_unit = u
-        for X in self.fwd:
-            if isinstance(X, ConvOp) and id(X) in conv_ok:
-                X.fb_segments = conv_ok[id(X)]
+            for m in u.members:
+                m.fb_unit = u
+        for X, sg in segs.items():
+            X.fb_segments = sg
 
     def _fb_table(self, X):
-        """mbx_bn_bwd_fused of consumer X's data gradient (kept alive in self._keep_fb)."""
+        """mbx_bn_bwd_fused of consumer X's data gradient (kept alive in self._keep)."""
         t = ops.BnBwdFused()
         t.barrier = self.bn_ws.data_ptr() + 4 * X.fb_bar_off
         t.n = len(X.fb_segments)
         t.step_poison = self.step_ctl.data_ptr()
         for i, (c_rel, m, c_in, n) in enumerate(X.fb_segments):
-            lead = m.fb_unit[0]
-            K_all = sum(q.K for q in m.fb_unit)
-            ko = m.y_view.ch_off                                         # the member's first channel inside the unit's [M, K_all] tensors
-            assert m.y_view.ld == K_all and m.dy_view.ld == K_all and lead.fb_acc_off >= 0
+            u = m.unit
+            ko = m.y_view.ch_off                                         # the member's first channel inside the unit's [M, K] tensors
+            assert m.y_view.ld == u.K and m.dy_view.ld == u.K and u.lead.fb_acc_off >= 0
             t.c_begin[i] = c_rel
-            t.y[i], t.ld_y[i] = m.y_view.buf.data_ptr() + 2 * (ko + c_in), K_all
-            t.dy[i], t.ld_dy[i] = m.dy_view.buf.data_ptr() + 2 * (ko + c_in), K_all
+            t.y[i], t.ld_y[i] = m.y_view.buf.data_ptr() + 2 * (ko + c_in), u.K
+            t.dy[i], t.ld_dy[i] = m.dy_view.buf.data_ptr() + 2 * (ko + c_in), u.K
             t.mean[i] = self.bn_mean.data_ptr() + 4 * (m.beta_off + c_in)
             t.rstd[i] = self.bn_rstd.data_ptr() + 4 * (m.beta_off + c_in)
             t.beta[i] = self.Bt.data_ptr() + 4 * (m.beta_off + c_in)
             t.dbeta[i] = self.Btg.data_ptr() + 4 * (m.beta_off + c_in)
-            t.acc[i], t.acc_ld[i] = self.bn_ws.data_ptr() + 4 * (lead.fb_acc_off + ko + c_in), K_all
+            t.acc[i], t.acc_ld[i] = self.bn_ws.data_ptr() + 4 * (u.lead.fb_acc_off + ko + c_in), u.K
             t.relu[i] = int(m.relu)
-        self._keep_fb = getattr(self, "_keep_fb", []) + [t]
+        self._keep.append(t)
         return t
 
     def _bw_table(self, X):
-        """mbx_bn_bwd_stats of consumer X's data gradient (kept alive in self._keep_bw)."""
+        """mbx_bn_bwd_stats of consumer X's data gradient (kept alive in self._keep)."""
         t = _lib.BnBwdStats()
         t.n, t.rows_mod = len(X.bw_segments), STATS_ROWS
         for i, (c_rel, m, c_in, n) in enumerate(X.bw_segments):
-            lead = m.bw_unit[0]
-            K_all = sum(q.K for q in m.bw_unit)
-            ko = m.y_view.ch_off                                         # the member's first channel inside the unit's [M, K_all] tensors
+            u = m.unit
+            ko = m.y_view.ch_off                                         # the member's first channel inside the unit's [M, K] tensors
             t.c_begin[i] = c_rel
-            t.y[i], t.ld_y[i] = m.y_view.buf.data_ptr() + 2 * (ko + c_in), K_all
+            t.y[i], t.ld_y[i] = m.y_view.buf.data_ptr() + 2 * (ko + c_in), u.K
             t.relu_thr[i] = self.bn_thr.data_ptr() + 4 * (m.beta_off + c_in)
-            t.stats[i], t.stats_ld[i] = self.bn_ws.data_ptr() + 4 * (lead.bw_rows_off + 2 * (ko + c_in)), K_all
-        self._keep_bw = getattr(self, "_keep_bw", []) + [t]
+            t.stats[i], t.stats_ld[i] = self.bn_ws.data_ptr() + 4 * (u.lead.bw_rows_off + 2 * (ko + c_in)), u.K
+        self._keep.append(t)
         return t
 
     # ------------------------------------------------------------------ descriptors
@@ -932,30 +867,15 @@ class Net:
                 self._i5_used += n
             if os.environ.get("MBX_NO_2STAGE") == "1":                     # bisecting aid: 3-deep-ring twins of the 2-deep tiles
                 d.tile_config = {9: 7, 10: 2, 11: 5, 12: 2, 13: 8, 14: 1}.get(d.tile_config, d.tile_config)
-            # few channels on a large map (the stem's 3x3 layers, forward and data gradient): the direct launch stages each
-            # pixel patch once instead of gathering it nine times (by rule, not by the table; bit-identical outputs)
-            if over is not None:
-                pass
-            elif ops.direct3_applies(d):
-                d.tile_config, d.work_counter = ops.DIRECT3_TILE_CONFIG, None
-                _lib.check(_lib.lib().mbx_conv_supported(C.byref(d)), "direct 3x3 " + op.name)
-            elif ops.directw_applies(d) and not (what == "fwd" and d.stats_partial and getattr(op, "group", None) is not None
-                                                 and len(op.group.members) == 2 and os.environ.get("MBX_CONV_PAIR", "1") != "0"):
-                # few channels on a NARROW map (block35's 3x3 layers, 35 x 35): the whole-width direct launch -- except for the
-                # two sibling FORWARD convolutions of a batch-norm group in training, which the implicit GEMM runs as ONE pair
-                # launch (21.7 us against 12.0 + 11.3 as two direct launches: these launches are latency-bound)
-                d.tile_config, d.work_counter = ops.DIRECTW_TILE_CONFIG, None
-                _lib.check(_lib.lib().mbx_conv_supported(C.byref(d)), "direct 3x3 (whole-width) " + op.name)
-            elif ops.pwres_applies(d):
-                # the 1x1 launches whose time is their epilogue's trunk traffic (residual "up" forward, accumulate + mask data
-                # gradients): pixels resident, filter streamed, one small epilogue per 128 output channels (by rule; bit-identical)
-                d.tile_config, d.work_counter = ops.PWRES_TILE_CONFIG, None
-                _lib.check(_lib.lib().mbx_conv_supported(C.byref(d)), "pixel-resident 1x1 " + op.name)
-            elif ops.resident_applies(d):
-                # many channels on a SMALL map with a multi-tap filter (block17's 1x7 / 7x1 layers, forward and data gradient): the
-                # resident-image launch stages each image once instead of gathering it once per tap (by rule; bit-identical outputs)
-                d.tile_config, d.work_counter = ops.RESIDENT_TILE_CONFIG, None
-                _lib.check(_lib.lib().mbx_conv_supported(C.byref(d)), "resident image " + op.name)
+            # the launches chosen by rule, not by the table (ops.launch_rule) -- except for the two sibling FORWARD convolutions
+            # of a batch-norm group in training, which the implicit GEMM runs as ONE pair launch where the rule would pick the
+            # whole-width direct launch (21.7 us against 12.0 + 11.3 as two direct launches: these launches are latency-bound)
+            pair = (what == "fwd" and bool(d.stats_partial) and op.group is not None and len(op.group.members) == 2
+                    and os.environ.get("MBX_CONV_PAIR", "1") != "0")
+            rule = ops.launch_rule(d, pair) if over is None else None
+            if rule is not None:
+                d.tile_config, d.work_counter = rule[0], None
+                _lib.check(_lib.lib().mbx_conv_supported(C.byref(d)), rule[1] + " " + op.name)
         return d
 
     def _build_forward_launches(self):
@@ -965,149 +885,11 @@ class Net:
         st = lambda: torch.cuda.current_stream().cuda_stream
         for op in self.fwd:
             if isinstance(op, PoolOp):
-                if not getattr(op, "fused_fwd", False):          # (else: its producer's BN apply writes the pooled tensor)
+                if not op.fused_fwd:          # (else: its producer's BN apply writes the pooled tensor)
                     L.append(op.forward)
                 continue
-            if op.kind == "bn" and op.group is not None:
-                # member of a batch-norm group: its convolution writes its channel slice of the group's [M, K] tensor and its
-                # own statistics partials; the LAST member's launch is followed by ONE finalize and ONE apply for the group
-                g = op.group
-                i = g.members.index(op)
-                use16 = self.atomic_stats
-                if use16:
-                    d = self._tune(op, self._desc(op, op.y_view, stats=self.stats16[op.stats16_off:], stats_rows_mod=STATS_ROWS,
-                                                  stats_ld=g.K), "fwd")
-                else:
-                    d = self._tune(op, self._desc(op, op.y_view, stats=self.stats_scratch[op.stats_off:]), "fwd")
-                g.rows[i] = ops.conv_stats_rows(d)
-                assert use16 or g.rows[i] * op.K * 2 <= (g.stats_off[i + 1] - g.stats_off[i] if i + 1 < len(g.members) else 1 << 62)
-                g.fwd_desc[i] = d
-                if i + 1 < len(g.members):
-                    # (a group of two whose convolutions resolve to the same small-tile kernel run as ONE launch, issued with the
-                    # last member: mbx_conv_pair; decided below, when both descriptors exist)
-                    L.append(lambda d=d, op=op, g=g: None if g.pair_fwd else _lib.check(l.mbx_conv(C.byref(d), st()), op.name))
-                    continue
-                if len(g.members) == 2 and torch.device(self.dev).type == "cuda" and os.environ.get("MBX_CONV_PAIR", "1") != "0":
-                    g.pair_fwd = l.mbx_conv_pair(C.byref(g.fwd_desc[0]), C.byref(d), st()) == 0        # (a real launch, like the tuner's)
-                lead, n = g.members[0], len(g.members)
-                parts = (C.c_void_p * n)(*[self.stats_scratch.data_ptr() + 4 * o for o in g.stats_off])
-                rows_a, cs_a = (C.c_int32 * n)(*g.rows), (C.c_int32 * n)(*[m.K for m in g.members])
-                base, amap = g.chan_map([m.out for m in g.members])
-                a_ptr = op.out.buf.data_ptr() + 2 * base
-                mean, rstd = self._sl(self.bn_mean, lead.beta_off, g.K), self._sl(self.bn_rstd, lead.beta_off, g.K)
-                mm, mv = self._sl(self.MM, lead.beta_off, g.K), self._sl(self.MV, lead.beta_off, g.K)
-                var, beta = self._sl(self.bn_var, lead.beta_off, g.K), self._sl(self.Bt, lead.beta_off, g.K)
-                thr = self._sl(self.bn_thr, lead.beta_off, g.K)
-                s16 = self.stats16[lead.stats16_base:]
-
-                def run(d=d, op=op, g=g, parts=parts, rows_a=rows_a, cs_a=cs_a, amap=amap, a_ptr=a_ptr, mean=mean, rstd=rstd,
-                        mm=mm, mv=mv, var=var, beta=beta, n=n, use16=use16, thr=thr, s16=s16):
-                    s = st()
-                    if g.pair_fwd:
-                        _lib.check(l.mbx_conv_pair(C.byref(g.fwd_desc[0]), C.byref(d), s), "pair " + op.name)
-                    else:
-                        _lib.check(l.mbx_conv(C.byref(d), s), op.name)
-                    decay = self.bn_decay
-                    if self.defer_moving:
-                        mm, mv, decay = None, var, -1.0
-                    if use16:
-                        # every member ADDED its tile sums into the group's 16 rows: the apply launch reduces them itself
-                        _lib.check(l.mbx_bn_apply_fused_mapped(s16.data_ptr(), STATS_ROWS, op.M, BN_EPS, decay, g.y.data_ptr(), op.M,
-                                                               g.K, beta.data_ptr(), int(op.relu), a_ptr, op.out.ld, C.byref(amap),
-                                                               mean.data_ptr(), rstd.data_ptr(), ops._p(mm), ops._p(mv),
-                                                               thr.data_ptr(), s), "bn_apply_fused_mapped")
-                        return
-                    _lib.check(l.mbx_bn_finalize_parts(parts, rows_a, cs_a, n, op.M, BN_EPS, decay, mean.data_ptr(), rstd.data_ptr(),
-                                                       ops._p(mm), ops._p(mv), s), "bn_finalize_parts")
-                    _lib.check(l.mbx_bn_apply_mapped(g.y.data_ptr(), op.M, g.K, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-                                                     int(op.relu), a_ptr, op.out.ld, C.byref(amap), s), "bn_apply_mapped")
-                L.append(run)
-            elif op.kind == "bn":
-                yv = op.y_view
-                fpool = getattr(op, "fused_pool", None)
-                use16 = self.atomic_stats and fpool is None          # (the fused apply + max-pool launch reads finalized statistics)
-                if use16:
-                    d = self._tune(op, self._desc(op, yv, stats=self.stats16[op.stats16_off:], stats_rows_mod=STATS_ROWS), "fwd")
-                else:
-                    d = self._tune(op, self._desc(op, yv, stats=self.stats_scratch), "fwd")
-                S_ = ops.splitk_slices(d, self.n_cus) if torch.device(self.dev).type == "cuda" else 0
-                if S_:
-                    # long K, few tiles (the 3x3 head convolutions on the 1536-channel map): K slices + a reduce launch
-                    d.tile_config = ops.SPLITK_FLAG + S_
-                    # (a workspace per launch: the head scales run on their own streams, Net.forward)
-                    need = int(l.mbx_conv_splitk_workspace_bytes(C.byref(d)))
-                    ws = torch.empty(need // 4, dtype=torch.float32, device=self.dev)
-                    self._splitk_ws = getattr(self, "_splitk_ws", []) + [ws]
-                    d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel() * 4
-                    _lib.check(l.mbx_conv_supported(C.byref(d)), "split-K " + op.name)
-                rows = ops.conv_stats_rows(d)
-                mean, rstd = self._sl(self.bn_mean, op.beta_off, op.K), self._sl(self.bn_rstd, op.beta_off, op.K)
-                mm, mv = self._sl(self.MM, op.beta_off, op.K), self._sl(self.MV, op.beta_off, op.K)
-                beta = self._sl(self.Bt, op.beta_off, op.K)
-                out = op.out
-
-                var = self._sl(self.bn_var, op.beta_off, op.K)
-                thr = self._sl(self.bn_thr, op.beta_off, op.K)
-                s16 = self.stats16[op.stats16_off:]
-
-                if fpool is not None:
-                    fpool.fused_fwd = True
-                # the layer's BN apply as the tail of the convolution launch (mbx_conv_desc.bn_apply), where the library has it
-                fd = ba = None
-                if use16 and self.fuse_apply and not S_ and torch.device(self.dev).type == "cuda" and out.img_stride == out.H * out.W * out.ld \
-                        and (not os.environ.get("MBX_FUSE_APPLY_ONLY") or re.search(os.environ["MBX_FUSE_APPLY_ONLY"], op.name)):
-                    ba = ops.BnApplyDesc()
-                    ba.barrier = self._fwd_barrier_base + ops.GRID_BARRIER_BYTES * self._fwd_barriers_used
-                    ba.a, ba.ld_a, ba.beta, ba.mean, ba.rstd = out.ptr, out.ld, beta.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-                    ba.relu_thr, ba.relu, ba.eps, ba.step_poison = thr.data_ptr(), int(op.relu), BN_EPS, self.step_ctl.data_ptr()
-                    fd = ops.ConvDesc.from_buffer_copy(d)
-                    fd.bn_apply = C.addressof(ba)
-                    fd.work_counter = None                   # (static deal: fused_bn.h)
-                    if l.mbx_conv_supported(C.byref(fd)) == 0:
-                        assert self._fwd_barriers_used < self._n_fwd_barriers
-                        self._fwd_barriers_used += 1
-                        self.fused_apply_launches += 1
-                        self._keep_ba = getattr(self, "_keep_ba", []) + [ba]
-                    else:
-                        fd = ba = None
-
-                def run(d=d, rows=rows, op=op, mean=mean, rstd=rstd, mm=mm, mv=mv, beta=beta, out=out, var=var, fpool=fpool,
-                        use16=use16, thr=thr, s16=s16, fd=fd, ba=ba):
-                    s = st()
-                    decay = self.bn_decay
-                    if self.defer_moving:                    # store mode: batch variance -> bn_var, moving statistics untouched
-                        mm, mv, decay = None, var, -1.0
-                    if fd is not None and not self.no_onepass:
-                        # ONE launch: convolution, grid barrier, statistics, normalise + beta + relu of the tiles each workgroup wrote
-                        ba.moving_mean, ba.moving_var, ba.decay = ops._p(mm), ops._p(mv), decay
-                        fd.max_workgroups = self.cu_cap or self.bn_max_wg
-                        _lib.check(l.mbx_conv(C.byref(fd), s), op.name + " + bn apply")
-                        return
-                    _lib.check(l.mbx_conv(C.byref(d), s), op.name)
-                    if use16:
-                        _lib.check(l.mbx_bn_apply_fused_mapped(s16.data_ptr(), STATS_ROWS, op.M, BN_EPS, decay, op.y_view.ptr, op.M,
-                                                               op.K, beta.data_ptr(), int(op.relu), out.ptr, out.ld, None,
-                                                               mean.data_ptr(), rstd.data_ptr(), ops._p(mm), ops._p(mv),
-                                                               thr.data_ptr(), s), "bn_apply_fused_mapped")
-                        return
-                    if fpool is not None:
-                        # the activation feeds only a 3x3 / 2 max-pool: normalise and pool in one pass, never store it
-                        po = fpool.out
-                        _lib.check(l.mbx_bn_finalize(self.stats_scratch.data_ptr(), rows, op.K, op.M, BN_EPS, decay,
-                                                     mean.data_ptr(), rstd.data_ptr(), ops._p(mm), ops._p(mv), s), "bn_finalize")
-                        _lib.check(l.mbx_bn_apply_maxpool(op.y_view.ptr, out.N, out.H, out.W, op.K, mean.data_ptr(), rstd.data_ptr(),
-                                                          beta.data_ptr(), int(op.relu), po.ptr, po.img_stride, po.ld, po.H, po.W,
-                                                          fpool.argmax.data_ptr(), s), "bn_apply_maxpool")
-                        return
-                    # (timing probe of tools/whatif_probe.py: finalize only, `a` keeps the previous step's values)
-                    if self._probe_skip_apply and ("/block" in op.name or "/Block8" in op.name):
-                        _lib.check(l.mbx_bn_finalize(self.stats_scratch.data_ptr(), rows, op.K, op.M, BN_EPS, decay,
-                                                     mean.data_ptr(), rstd.data_ptr(), ops._p(mm), ops._p(mv), s), "fin")
-                        return
-                    _lib.check(l.mbx_bn_apply_fused(self.stats_scratch.data_ptr(), rows, op.M, BN_EPS, decay,
-                                                    op.y_view.ptr, op.M, op.K, beta.data_ptr(), int(op.relu), out.ptr, out.ld,
-                                                    mean.data_ptr(), rstd.data_ptr(), ops._p(mm), ops._p(mv), s), "bn_apply_fused")
-                L.append(run)
+            if op.kind == "bn":
+                L.append(self._bn_forward(op))
             elif op.kind == "frozen":
                 d = self._tune(op, self._desc(op, op.out, epilogue=ops.EPI_AFFINE, relu=op.relu,
                                               scale=self._sl(self.bn_scale, op.beta_off, op.K),
@@ -1116,7 +898,7 @@ class Net:
             elif op.kind == "residual":
                 d = self._tune(op, self._desc(op, op.out, epilogue=ops.EPI_RESIDUAL, relu=op.relu,
                                               shift=self._sl(self.W, op.b_off, op.K), skip=op.skip, rscale=op.rscale,
-                                              relu_bits=getattr(op, "relu_bits", None)), "fwd")
+                                              relu_bits=op.relu_bits), "fwd")
                 L.append(lambda d=d, op=op: _lib.check(l.mbx_conv(C.byref(d), st()), op.name))
             elif op.kind == "head":
                 d = self._desc(op, op.out, epilogue=ops.EPI_STORE_F32)
@@ -1126,6 +908,109 @@ class Net:
                     L.append(lambda: _lib.check(l.mbx_head_gather_all(self.head_table, len(self.heads), self.B, self.P,
                                                                       self.locs.data_ptr(), self.logits.data_ptr(), st()), "head_gather_all"))
         return L
+
+    def _bn_forward(self, op):
+        """The forward launch of one training-mode batch-norm convolution: the convolution, which writes its channel slice of
+        the unit's [M, K] tensor and its own statistics partials, and behind the unit's LAST member the ONE normalisation of
+        the unit.  Split-K, the fused max-pool and the fused apply tail are for units of one, the pair launch for units of two."""
+        l = _lib.lib()
+        st = lambda: torch.cuda.current_stream().cuda_stream
+        cuda = torch.device(self.dev).type == "cuda"
+        u = op.unit
+        i, n, single = u.members.index(op), len(u.members), len(u.members) == 1
+        fpool = op.fused_pool
+        use16 = self.atomic_stats and fpool is None          # (the fused apply + max-pool launch reads finalized statistics)
+        if use16:
+            d = self._desc(op, op.y_view, stats=self.stats16[op.stats16_off:], stats_rows_mod=STATS_ROWS, stats_ld=0 if single else u.K)
+        else:
+            d = self._desc(op, op.y_view, stats=self.stats_scratch[op.stats_off:])
+        d = self._tune(op, d, "fwd")
+        S_ = ops.splitk_slices(d, self.n_cus) if single and cuda else 0
+        if S_:
+            # long K, few tiles (the 3x3 head convolutions on the 1536-channel map): K slices + a reduce launch
+            d.tile_config = ops.SPLITK_FLAG + S_
+            # (a workspace per launch: the head scales run on their own streams, Net.forward)
+            need = int(l.mbx_conv_splitk_workspace_bytes(C.byref(d)))
+            ws = torch.empty(need // 4, dtype=torch.float32, device=self.dev)
+            self._keep.append(ws)
+            d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel() * 4
+            _lib.check(l.mbx_conv_supported(C.byref(d)), "split-K " + op.name)
+        rows = u.rows[i] = ops.conv_stats_rows(d)
+        assert use16 or i + 1 == n or rows * op.K * 2 <= u.stats_off[i + 1] - u.stats_off[i]
+        u.fwd_desc[i] = d
+        if i + 1 < n:
+            # (a unit of two whose convolutions resolve to the same small-tile kernel run as ONE launch, issued with the
+            # last member: mbx_conv_pair; decided below, when both descriptors exist)
+            return lambda: None if u.pair_fwd else _lib.check(l.mbx_conv(C.byref(d), st()), op.name)
+        if n == 2 and cuda and os.environ.get("MBX_CONV_PAIR", "1") != "0":
+            u.pair_fwd = l.mbx_conv_pair(C.byref(u.fwd_desc[0]), C.byref(d), st()) == 0        # (a real launch, like the tuner's)
+        K, M, out = u.K, op.M, op.out
+        mean, rstd, mm, mv, var, beta, thr = (self._sl(t, u.lead.beta_off, K) for t in
+                                              (self.bn_mean, self.bn_rstd, self.MM, self.MV, self.bn_var, self.Bt, self.bn_thr))
+        s16 = self.stats16[u.stats16_base:]
+        # (several members: the activations addressed through the unit's channel map)
+        a_ptr, a_ld, amap = u.target([m.out for m in u.members])
+        amap = None if amap is None else C.byref(amap)
+        parts = (C.c_void_p * n)(*[self.stats_scratch.data_ptr() + 4 * o for o in u.stats_off])
+        rows_a, cs_a = (C.c_int32 * n)(*u.rows), (C.c_int32 * n)(*[m.K for m in u.members])
+        if fpool is not None:
+            fpool.fused_fwd = True
+        # the layer's BN apply as the tail of the convolution launch (mbx_conv_desc.bn_apply), where the library has it
+        fd = ba = None
+        if single and use16 and self.fuse_apply and not S_ and cuda and out.img_stride == out.H * out.W * out.ld \
+                and (not os.environ.get("MBX_FUSE_APPLY_ONLY") or re.search(os.environ["MBX_FUSE_APPLY_ONLY"], op.name)):
+            ba = ops.BnApplyDesc()
+            ba.barrier = self._fwd_barrier_base + ops.GRID_BARRIER_BYTES * self._fwd_barriers_used
+            ba.a, ba.ld_a, ba.beta, ba.mean, ba.rstd = out.ptr, out.ld, beta.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+            ba.relu_thr, ba.relu, ba.eps, ba.step_poison = thr.data_ptr(), int(op.relu), BN_EPS, self.step_ctl.data_ptr()
+            fd = ops.ConvDesc.from_buffer_copy(d)
+            fd.bn_apply = C.addressof(ba)
+            fd.work_counter = None                   # (static deal: fused_bn.h)
+            if l.mbx_conv_supported(C.byref(fd)) == 0:
+                assert self._fwd_barriers_used < self._n_fwd_barriers
+                self._fwd_barriers_used += 1
+                self.fused_apply_launches += 1
+            else:
+                fd = ba = None
+
+        def run():
+            s = st()
+            # defer_moving: store mode -- batch variance -> bn_var, moving statistics untouched
+            mm_, mv_, decay = (None, var, -1.0) if self.defer_moving else (mm, mv, self.bn_decay)
+            if fd is not None and not self.no_onepass:
+                # ONE launch: convolution, grid barrier, statistics, normalise + beta + relu of the tiles each workgroup wrote
+                ba.moving_mean, ba.moving_var, ba.decay = ops._p(mm_), ops._p(mv_), decay
+                fd.max_workgroups = self.cu_cap or self.bn_max_wg
+                _lib.check(l.mbx_conv(C.byref(fd), s), op.name + " + bn apply")
+                return
+            if u.pair_fwd:
+                _lib.check(l.mbx_conv_pair(C.byref(u.fwd_desc[0]), C.byref(d), s), "pair " + op.name)
+            else:
+                _lib.check(l.mbx_conv(C.byref(d), s), op.name)
+            totals = (mean.data_ptr(), rstd.data_ptr(), ops._p(mm_), ops._p(mv_))
+            if use16:
+                # every member ADDED its tile sums into the unit's STATS_ROWS rows: the apply launch reduces them itself
+                _lib.check(l.mbx_bn_apply_fused_mapped(s16.data_ptr(), STATS_ROWS, M, BN_EPS, decay, u.y.data_ptr(), M, K,
+                                                       beta.data_ptr(), int(op.relu), a_ptr, a_ld, amap, *totals,
+                                                       thr.data_ptr(), s), "bn_apply_fused_mapped")
+            elif not single:
+                _lib.check(l.mbx_bn_finalize_parts(parts, rows_a, cs_a, n, M, BN_EPS, decay, *totals, s), "bn_finalize_parts")
+                _lib.check(l.mbx_bn_apply_mapped(u.y.data_ptr(), M, K, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
+                                                 int(op.relu), a_ptr, a_ld, amap, s), "bn_apply_mapped")
+            elif fpool is not None:
+                # the activation feeds only a 3x3 / 2 max-pool: normalise and pool in one pass, never store it
+                po = fpool.out
+                _lib.check(l.mbx_bn_finalize(self.stats_scratch.data_ptr(), rows, K, M, BN_EPS, decay, *totals, s), "bn_finalize")
+                _lib.check(l.mbx_bn_apply_maxpool(u.y.data_ptr(), out.N, out.H, out.W, K, mean.data_ptr(), rstd.data_ptr(),
+                                                  beta.data_ptr(), int(op.relu), po.ptr, po.img_stride, po.ld, po.H, po.W,
+                                                  fpool.argmax.data_ptr(), s), "bn_apply_maxpool")
+            elif self._probe_skip_apply and ("/block" in op.name or "/Block8" in op.name):
+                # (timing probe of tools/whatif_probe.py: finalize only, `a` keeps the previous step's values)
+                _lib.check(l.mbx_bn_finalize(self.stats_scratch.data_ptr(), rows, K, M, BN_EPS, decay, *totals, s), "fin")
+            else:
+                _lib.check(l.mbx_bn_apply_fused(self.stats_scratch.data_ptr(), rows, M, BN_EPS, decay, u.y.data_ptr(), M, K,
+                                                beta.data_ptr(), int(op.relu), a_ptr, a_ld, *totals, s), "bn_apply_fused")
+        return run
 
     # ------------------------------------------------------------------- backward
     def _gview(self, v: View) -> View:
@@ -1150,7 +1035,6 @@ class Net:
         arr = (_lib.Head * len(self.heads))()
         for j, op in enumerate(self.heads):
             cells, kk, off = op.head
-            op.head_grad = None
             if self.mode == "train":
                 op.head_grad = View(torch.zeros((op.M, self.head_ld), dtype=torch.bfloat16, device=self.dev),
                                     op.out.N, op.out.H, op.out.W, self.head_ld)
@@ -1246,96 +1130,8 @@ class Net:
                 else:
                     pre = None
             else:   # bn
-                dyv = op.dy_view
-                scale, db = 1.0, None
-                g = op.group
-                if g is not None and op is not g.members[-1]:
-                    pre = None                      # the group's ONE backward launch ran in front of its last member's data gradient
-                else:
-                    # (a group: the [M, K] tensors of all members, the gradient view addressed through the group's channel map)
-                    lead = op if g is None else g.members[0]
-                    Kb = K if g is None else g.K
-                    y_ptr, dy_ptr = (op.y_view.ptr, op.dy_view.ptr) if g is None else (g.y.data_ptr(), g.dy.data_ptr())
-                    fpool = getattr(op, "fused_pool", None)
-                    if fpool is not None:
-                        da = da_ptr = dmap = None
-                    elif g is None:
-                        da, da_ptr, dmap = self._gview(op.out), self._gview(op.out).ptr, None
-                    else:
-                        gviews = [self._gview(m.out) for m in g.members]
-                        assert all(v.buf is gviews[0].buf and v.ld == gviews[0].ld for v in gviews)
-                        base, cm = g.chan_map(gviews)
-                        da, da_ptr, dmap = gviews[0], gviews[0].buf.data_ptr() + 2 * base, C.byref(cm)
-                        self._keep = getattr(self, "_keep", []) + [cm]
-                    mean, rstd = self._sl(self.bn_mean, lead.beta_off, Kb), self._sl(self.bn_rstd, lead.beta_off, Kb)
-                    dbeta = self._sl(self.Btg, lead.beta_off, Kb)
-                    rows = l.mbx_bn_bwd_rows(M, Kb)
-                    beta = self._sl(self.Bt, lead.beta_off, Kb)
-                    ws_off = lead.bn_ws_off
-
-                    def pre_onepass(s, op=op, da=da, da_ptr=da_ptr, dmap=dmap, mean=mean, rstd=rstd, beta=beta, dbeta=dbeta, Kb=Kb, M=M,
-                                    y_ptr=y_ptr, dy_ptr=dy_ptr, ws_off=ws_off):
-                        # da and y are read once: the slice stays in registers across a grid barrier
-                        _lib.check(l.mbx_bn_bwd_onepass_mapped(da_ptr, da.ld, int(op.relu), y_ptr, M, Kb, mean.data_ptr(),
-                                                               rstd.data_ptr(), beta.data_ptr(), dbeta.data_ptr(),
-                                                               dy_ptr, self.bn_ws.data_ptr() + 4 * ws_off,
-                                                               self.cu_cap or self.bn_max_wg, self.step_ctl.data_ptr(), dmap, s),
-                                   "bn_bwd_onepass")
-
-                    def pre(s, op=op, da=da, da_ptr=da_ptr, dmap=dmap, mean=mean, rstd=rstd, beta=beta, dbeta=dbeta, rows=rows, Kb=Kb,
-                            M=M, y_ptr=y_ptr, dy_ptr=dy_ptr):
-                        # relu mask recomputed from y (a = NULL): the activation is not re-read in the backward pass
-                        _lib.check(l.mbx_bn_bwd_reduce_mapped(da_ptr, da.ld, None, 0, int(op.relu), y_ptr, M, Kb,
-                                                              mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(),
-                                                              self.bwd_scratch.data_ptr(), dmap, s), "bn_bwd_reduce")
-                        _lib.check(l.mbx_bn_bwd_finalize(self.bwd_scratch.data_ptr(), rows, Kb, M, dbeta.data_ptr(),
-                                                         self.m12.data_ptr(), s), "bn_bwd_finalize")
-                        _lib.check(l.mbx_bn_bwd_apply_mapped(da_ptr, da.ld, None, 0, int(op.relu), y_ptr, M, Kb,
-                                                             mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), self.m12.data_ptr(),
-                                                             dy_ptr, dmap, s), "bn_bwd_apply")
-                    if op.bw_unit is not None:
-                        # the sums were ADDED by the data gradient(s) that wrote da (their launches ran earlier in this pass)
-                        thr = self._sl(self.bn_thr, lead.beta_off, Kb)
-                        rows_off = lead.bw_rows_off
-
-                        def pre(s, da=da, da_ptr=da_ptr, dmap=dmap, mean=mean, rstd=rstd, thr=thr, dbeta=dbeta, Kb=Kb, M=M,
-                                y_ptr=y_ptr, dy_ptr=dy_ptr, rows_off=rows_off):
-                            _lib.check(l.mbx_bn_bwd_apply_rows(self.bn_ws.data_ptr() + 4 * rows_off, STATS_ROWS, da_ptr, da.ld, y_ptr, M, Kb,
-                                                               mean.data_ptr(), rstd.data_ptr(), thr.data_ptr(), dbeta.data_ptr(),
-                                                               dy_ptr, dmap, s), "bn_bwd_apply_rows")
-                    if fpool is not None:
-                        gy = self._gview(fpool.out)
-                        rows = l.mbx_bn_bwd_rows_pooled(fpool.x.N, fpool.x.H, fpool.x.W, Kb)     # (<= the plain form's: bwd_scratch fits)
-                        assert 0 < rows * Kb * 2 <= self.bwd_scratch.numel()
-
-                        def pre(s, op=op, gy=gy, fpool=fpool, mean=mean, rstd=rstd, beta=beta, dbeta=dbeta, rows=rows, Kb=Kb, M=M,
-                                y_ptr=y_ptr, dy_ptr=dy_ptr):
-                            geo = (gy.ptr, gy.img_stride, gy.ld, fpool.argmax.data_ptr(), fpool.x.N, fpool.x.H, fpool.x.W, fpool.out.H,
-                                   fpool.out.W, int(op.relu), y_ptr, Kb, mean.data_ptr(), rstd.data_ptr(), beta.data_ptr())
-                            _lib.check(l.mbx_bn_bwd_reduce_pooled(*geo, self.bwd_scratch.data_ptr(), s), "bn_bwd_reduce_pooled")
-                            _lib.check(l.mbx_bn_bwd_finalize(self.bwd_scratch.data_ptr(), rows, Kb, M, dbeta.data_ptr(),
-                                                             self.m12.data_ptr(), s), "bn_bwd_finalize")
-                            _lib.check(l.mbx_bn_bwd_apply_pooled(*geo, self.m12.data_ptr(), dy_ptr, s), "bn_bwd_apply_pooled")
-                if pre is not None and op.bw_unit is None and (op.bn_ws_off if g is None else g.members[0].bn_ws_off) >= 0:
-                    # chosen at CALL time: Trainer.check_health() falls back to the three launches (and re-captures its
-                    # graphs) when a grid barrier has timed out -- e.g. RCCL kernels holding more CUs than bn_max_wg allows for
-                    def pre(s, one=pre_onepass, three=pre):
-                        (three if self.no_onepass else one)(s)
-                    if os.environ.get("MBX_PROBE_BN_APPLY_ONLY") == "1":
-                        # timing probe (WRONG results): what a batch-norm backward that is ONE streaming launch would cost --
-                        # the apply launch of the three-launch form on stale totals
-                        def pre(s, op=op, da=da, da_ptr=da_ptr, dmap=dmap, mean=mean, rstd=rstd, beta=beta, Kb=Kb, M=M, y_ptr=y_ptr,
-                                dy_ptr=dy_ptr):
-                            _lib.check(l.mbx_bn_bwd_apply_mapped(da_ptr, da.ld, None, 0, int(op.relu), y_ptr, M, Kb,
-                                                                 mean.data_ptr(), rstd.data_ptr(), beta.data_ptr(), self.m12.data_ptr(),
-                                                                 dy_ptr, dmap, s), "bn_bwd_apply")
-            if op.kind == "bn" and op.fb_unit is not None and pre is not None:
-                # this layer's backward runs as the tail of the data gradient(s) that wrote its activation gradient (their
-                # launches came earlier in this pass): nothing to launch here -- unless the trainer fell back (call time)
-                def pre(s, split=pre):
-                    if self.no_onepass:
-                        split(s)
-                self.fused_bwd_layers += 1
+                dyv, scale, db = op.dy_view, 1.0, None
+                pre = self._bn_backward(op)
             ddesc = fdesc = None
             if op.need_dx:
                 gx = self._gview(op.x)
@@ -1394,7 +1190,7 @@ class Net:
             job.scale = float(scale)
             job.dw, job.db = dw.data_ptr(), (None if db is None else db.data_ptr())
 
-            grp = getattr(op, "group", None) if op.kind == "bn" else None
+            grp = op.group
             if grp is not None and ddesc is not None:
                 grp.dgrad_desc[grp.members.index(op)] = ddesc
 
@@ -1421,12 +1217,96 @@ class Net:
             self.bwd_jobs.append(job)
         if torch.device(self.dev).type == "cuda" and os.environ.get("MBX_CONV_PAIR", "1") != "0":
             for grp in self.bn_groups:
-                if len(grp.members) == 2 and len(grp.dgrad_desc) == 2 and not any(getattr(m, "fdesc", None) is not None for m in grp.members):
+                if len(grp.members) == 2 and len(grp.dgrad_desc) == 2 and not any(m.fdesc is not None for m in grp.members):
                     grp.pair_bwd = l.mbx_conv_pair(C.byref(grp.dgrad_desc[1]), C.byref(grp.dgrad_desc[0]), st()) == 0
         assert not self.pending_acc, "a residual block's input gradient was never written"
         self.bwd_launches = L
         self.fwd_launches = self._build_forward_launches()
         self._default_groups = None
+
+    def _bn_backward(self, op):
+        """The batch-norm backward issued in front of op's data gradient: a callable taking the stream, or None.  The form is
+        chosen HERE and nowhere else, the first that applies:
+          1. op is not the last member of its unit: nothing (the unit's ONE backward runs in front of its last member's data
+             gradient, the first in backward order);
+          2. the layer feeds a fused max-pool (_pool_producer): the pooled three-launch form;
+          3. op.bw_unit: one streaming launch on the sums the data gradients added (_plan_bw_stats);
+          4. the unit was granted a workspace (bn_ws_off): one-launch or three-launch, chosen at CALL time (no_onepass) --
+             or, under MBX_PROBE_BN_APPLY_ONLY=1, the timing probe in their place;
+          5. otherwise the three-launch form.
+        Where the data gradients of the unit's consumers run its backward as their tail (op.fb_unit, _plan_fused_bwd), the
+        chosen form is launched only once the trainer has fallen back (no_onepass, call time)."""
+        l = _lib.lib()
+        u = op.unit
+        if op is not u.members[-1]:
+            return None
+        K, M, relu, fpool = u.K, op.M, int(op.relu), op.fused_pool
+        rows3 = l.mbx_bn_bwd_rows(M, K)
+        y_ptr, dy_ptr, scratch, m12 = u.y.data_ptr(), u.dy.data_ptr(), self.bwd_scratch.data_ptr(), self.m12.data_ptr()
+        mean, rstd, beta, dbeta, thr = (self._sl(t, u.lead.beta_off, K).data_ptr() for t in
+                                        (self.bn_mean, self.bn_rstd, self.Bt, self.Btg, self.bn_thr))
+        da_ptr = da_ld = dmap = None                     # (a fused pool: the gradient is gathered from the pool's output gradient)
+        if fpool is None:
+            # (several members: the gradient views addressed through the unit's channel map)
+            da_ptr, da_ld, dmap = u.target([self._gview(m.out) for m in u.members])
+            dmap = None if dmap is None else C.byref(dmap)
+
+        def three(s):
+            # relu mask recomputed from y (a = NULL): the activation is not re-read in the backward pass
+            _lib.check(l.mbx_bn_bwd_reduce_mapped(da_ptr, da_ld, None, 0, relu, y_ptr, M, K, mean, rstd, beta, scratch, dmap, s),
+                       "bn_bwd_reduce")
+            _lib.check(l.mbx_bn_bwd_finalize(scratch, rows3, K, M, dbeta, m12, s), "bn_bwd_finalize")
+            apply_only(s)
+
+        def apply_only(s):
+            _lib.check(l.mbx_bn_bwd_apply_mapped(da_ptr, da_ld, None, 0, relu, y_ptr, M, K, mean, rstd, beta, m12, dy_ptr, dmap, s),
+                       "bn_bwd_apply")
+
+        if fpool is not None:
+            gy = self._gview(fpool.out)
+            rows = l.mbx_bn_bwd_rows_pooled(fpool.x.N, fpool.x.H, fpool.x.W, K)     # (<= the plain form's: bwd_scratch fits)
+            assert 0 < rows * K * 2 <= self.bwd_scratch.numel()
+
+            def form(s):
+                geo = (gy.ptr, gy.img_stride, gy.ld, fpool.argmax.data_ptr(), fpool.x.N, fpool.x.H, fpool.x.W, fpool.out.H,
+                       fpool.out.W, relu, y_ptr, K, mean, rstd, beta)
+                _lib.check(l.mbx_bn_bwd_reduce_pooled(*geo, scratch, s), "bn_bwd_reduce_pooled")
+                _lib.check(l.mbx_bn_bwd_finalize(scratch, rows, K, M, dbeta, m12, s), "bn_bwd_finalize")
+                _lib.check(l.mbx_bn_bwd_apply_pooled(*geo, m12, dy_ptr, s), "bn_bwd_apply_pooled")
+        elif op.bw_unit is not None:
+            rows_ptr = self.bn_ws.data_ptr() + 4 * u.lead.bw_rows_off
+
+            def form(s):
+                # the sums were ADDED by the data gradient(s) that wrote da (their launches ran earlier in this pass)
+                _lib.check(l.mbx_bn_bwd_apply_rows(rows_ptr, STATS_ROWS, da_ptr, da_ld, y_ptr, M, K, mean, rstd, thr, dbeta,
+                                                   dy_ptr, dmap, s), "bn_bwd_apply_rows")
+        elif u.lead.bn_ws_off >= 0:
+            ws_ptr = self.bn_ws.data_ptr() + 4 * u.lead.bn_ws_off
+
+            def one(s):
+                # da and y are read once: the slice stays in registers across a grid barrier
+                _lib.check(l.mbx_bn_bwd_onepass_mapped(da_ptr, da_ld, relu, y_ptr, M, K, mean, rstd, beta, dbeta, dy_ptr, ws_ptr,
+                                                       self.cu_cap or self.bn_max_wg, self.step_ctl.data_ptr(), dmap, s),
+                           "bn_bwd_onepass")
+
+            def form(s):
+                # chosen at CALL time: Trainer.check_health() falls back to the three launches (and re-captures its
+                # graphs) when a grid barrier has timed out -- e.g. RCCL kernels holding more CUs than bn_max_wg allows for
+                (three if self.no_onepass else one)(s)
+            if os.environ.get("MBX_PROBE_BN_APPLY_ONLY") == "1":
+                # timing probe (WRONG results): what a batch-norm backward that is ONE streaming launch would cost --
+                # the apply launch of the three-launch form on stale totals
+                form = apply_only
+        else:
+            form = three
+        if op.fb_unit is None:
+            return form
+        self.fused_bwd_layers += 1
+
+        def unless_fused(s):
+            if self.no_onepass:
+                form(s)
+        return unless_fused
 
     def _pool_producer(self, pool):
         """The batch-norm layer whose activation is `pool`'s input if the pool's backward can ride in that layer's three-launch
@@ -1589,6 +1469,7 @@ class PoolOp:
     def __init__(self, net, kind, x: View, out: View, k, stride, pad):
         self.net, self.kind, self.x, self.out, self.k, self.stride, self.pad = net, kind, x, out, k, stride, pad
         self.argmax = None
+        self.fused_fwd = False      # its producer's BN apply writes the pooled tensor (Net._bn_forward)
         if kind == "max" and net.mode == "train" and not net.fine_tune:
             self.argmax = torch.zeros((out.N, out.H, out.W, out.C), dtype=torch.uint8, device=net.dev)
 

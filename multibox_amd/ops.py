@@ -312,6 +312,28 @@ def pwres_applies(desc: ConvDesc, min_pixels=4096):
     return desc.N * desc.H_out * desc.W_out >= int(os.environ.get("MBX_PWRES_MIN_PIXELS", min_pixels))
 
 
+def launch_rule(desc: ConvDesc, pair=False):
+    """The launch a convolution gets BY RULE instead of a tile of the measured table (bit-identical outputs): (tile_config,
+    label) of the first rule that applies, or None.  `pair`: the caller runs this convolution and a sibling as one pair
+    launch of the implicit GEMM, which the whole-width direct launch cannot be part of.  The caller asks mbx_conv_supported."""
+    # few channels on a large map (the stem's 3x3 layers, forward and data gradient): the direct launch stages each
+    # pixel patch once instead of gathering it nine times
+    if direct3_applies(desc):
+        return DIRECT3_TILE_CONFIG, "direct 3x3"
+    # few channels on a NARROW map (block35's 3x3 layers, 35 x 35): the whole-width direct launch
+    if directw_applies(desc) and not pair:
+        return DIRECTW_TILE_CONFIG, "direct 3x3 (whole-width)"
+    # the 1x1 launches whose time is their epilogue's trunk traffic (residual "up" forward, accumulate + mask data
+    # gradients): pixels resident, filter streamed, one small epilogue per 128 output channels
+    if pwres_applies(desc):
+        return PWRES_TILE_CONFIG, "pixel-resident 1x1"
+    # many channels on a SMALL map with a multi-tap filter (block17's 1x7 / 7x1 layers, forward and data gradient): the
+    # resident-image launch stages each image once instead of gathering it once per tap
+    if resident_applies(desc):
+        return RESIDENT_TILE_CONFIG, "resident image"
+    return None
+
+
 def splitk_slices(desc: ConvDesc, n_cus=256):
     """Split-K slices for a forward convolution by rule (0: none): long K (>= 8192) and at most 96 tiles of 128 x 64, i.e.
     less than half the CUs busy for hundreds of K steps -- the two 3x3 head convolutions on the 1536-channel feature map

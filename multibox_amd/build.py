@@ -24,6 +24,7 @@ SOURCES = {
     "cocomatch.hip": ["-ffp-contract=off"],
     "cocoaccum.hip": ["-ffp-contract=off"],
     "conv.hip": ["-munsafe-fp-atomics"],
+    "wgrad.hip": ["-munsafe-fp-atomics"],
     # (the atomic optimizer turns the tile-fetch atomicAdd of conv_igemm5_kernel into scan + v_readfirstlane of the result,
     # i.e. waits for it at the issue; without it the wait sits where the value is published)
     "conv5.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],

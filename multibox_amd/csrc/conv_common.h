@@ -1,7 +1,7 @@
 // The kernel parameter block, the launch interface and the device helpers shared by the convolution translation units:
-// conv.hip (igemm3, weight gradients, the C entry points and conv_impl, the dispatcher) and one file per launch family --
-// conv5.hip (persistent igemm5), conv7.hip (panel-resident pointwise igemm7), convd.hip (direct 3x3 / whole-width / stem),
-// convr.hip (resident-image and pixel-resident pointwise).  gfx950 only.
+// conv.hip (igemm3, the C entry points and conv_impl, the dispatcher), wgrad.hip (the weight gradients) and one file per
+// launch family -- conv5.hip (persistent igemm5), conv7.hip (panel-resident pointwise igemm7), convd.hip (direct 3x3 /
+// whole-width / stem), convr.hip (resident-image and pixel-resident pointwise).  gfx950 only.
 #pragma once
 #include "common.h"
 #include "grid_barrier.h"
@@ -125,6 +125,26 @@ constexpr int kThreads = 256;
 // CUs the persistent launches size their grids by (and the grouped weight gradient plans for); no device visible -- planning
 // or mbx_conv_supported on a CPU-only host: MI355X
 inline int conv_cus() { const int n = mbx_cu_count(); return n ? n : 256; }
+
+// magic number + shift of the kernels' division by d (fast_div)
+inline void set_magic(unsigned d, unsigned& mg, unsigned& sh) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  sh = 31 + l;
+  mg = (unsigned)((1ull << sh) / d + 1);
+}
+
+// what every entry point that takes a mbx_conv_desc checks first (forward / data gradient and weight gradient alike)
+inline int check_desc(const mbx_conv_desc* d) {
+  if (!d || !d->x || !d->N || d->N < 0) return MBX_ERR_INVALID_ARG;
+  if (d->C_in <= 0 || d->C_in % 8 || d->ldx % 8 || d->ldx < d->C_in) return MBX_ERR_INVALID_ARG;
+  if (d->R <= 0 || d->S <= 0 || d->C_out <= 0 || d->H_out <= 0 || d->W_out <= 0) return MBX_ERR_INVALID_ARG;
+  if (d->stride != 1 && d->stride != 2) return MBX_ERR_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(d->x) & 15)) return MBX_ERR_INVALID_ARG;
+  const long long xe = (long long)d->N * d->x_img_stride;
+  if (xe >= (1LL << 30) || (long long)d->N * d->H_out * d->W_out >= (1LL << 31)) return MBX_ERR_UNSUPPORTED;
+  return MBX_OK;
+}
 
 // sum over the 16 lanes of a DPP row (lanes sharing lane >> 4): four v_add_f32_dpp row_ror, every lane ends up with the
 // row sum -- no LDS traffic (ds_bpermute shuffles made the epilogue VALU/LDS-bound).  Written as ONE asm block of fused

@@ -107,6 +107,66 @@ def test_single_layer_wgrad_forward_dgrad_exact(T, name):
     assert _outside_zero(torch, dx)
 
 
+# M = 36 (less than one 64-pixel step), the linear 1x1 path, general addressing with C_out below one narrow tile's width
+WGRAD_EDGE_CASES = ["2x2_valid_128_96", "1x1_320_96", "3x3_same_32_48"]
+
+
+@pytest.mark.parametrize("name", WGRAD_EDGE_CASES)
+def test_single_layer_wgrad_no_bias_exact(T, name):
+    """mbx_conv_wgrad with db = NULL (the instantiations without the bias gradient, which the test above never launches) at
+    tile_config 0..11: dw equals the integer reference after one launch and exactly twice it after two."""
+    torch = T
+    from multibox_amd import ops
+    c = E.conv_case(name)
+    N, H, W, Ci, Co, R, S, st, pads = c["g"]
+    Ho, Wo = c["Ho"], c["Wo"]
+    _exact(2 * c["dw"])
+    xb = _upload(torch, ops, c["x"], 8, 8)
+    dyb = _upload(torch, ops, c["dy"], 8, 8)
+    dw = torch.zeros((Co, R, S, Ci), dtype=torch.float32, device="cuda")
+    d = ops.make_desc(xb, None, Co, R, S, st, pads[0], pads[1], ops.View.alloc(N, Ho, Wo, Co))
+    ref_w = c["dw"].float()
+    for cfg in range(12):
+        d.tile_config = cfg
+        dw.zero_()
+        for rep in (1, 2):
+            ops.conv_wgrad(d, dyb, dw, None)
+            torch.cuda.synchronize()
+            assert torch.equal(dw.cpu(), rep * ref_w), "dw tile_config %d launch %d: %d elements differ" % (
+                cfg, rep, int((dw.cpu() != rep * ref_w).sum()))
+
+
+@pytest.mark.parametrize("name", WGRAD_EDGE_CASES)
+def test_single_layer_wgrad_nondense_dy_exact(T, name):
+    """mbx_conv_wgrad_scaled on a dy with a gap of three pixel rows between images (dy_img_stride = (H_out W_out + 3) ld_dy,
+    the gap filled with a non-zero value), at tile_config 0, 2, 7 and 9 -- at 7 and 9 the library must fall back to the wide
+    tile, the narrow one needs dense dy: dw and db equal the integer reference, i.e. no gap row is ever summed."""
+    torch = T
+    from multibox_amd import ops, _lib
+    l = _lib.lib()
+    c = E.conv_case(name)
+    N, H, W, Ci, Co, R, S, st, pads = c["g"]
+    Ho, Wo = c["Ho"], c["Wo"]
+    _exact(c["dw"]), _exact(c["db"])
+    assert Co % 8 == 0
+    xb = _upload(torch, ops, c["x"], 8, 8)
+    ld, rows = Co, Ho * Wo + 3
+    dyg = torch.full((N, rows, ld), 3.0, dtype=torch.bfloat16, device="cuda")
+    dyg[:, :Ho * Wo, :] = c["dy"].reshape(N, Ho * Wo, Co).to(torch.bfloat16).cuda()
+    dw = torch.zeros((Co, R, S, Ci), dtype=torch.float32, device="cuda")
+    db = torch.zeros((Co,), dtype=torch.float32, device="cuda")
+    d = ops.make_desc(xb, None, Co, R, S, st, pads[0], pads[1], ops.View.alloc(N, Ho, Wo, Co))
+    ref_w, ref_b = c["dw"].float(), c["db"].float()
+    for cfg in (0, 2, 7, 9):
+        d.tile_config = cfg
+        dw.zero_(); db.zero_()
+        _lib.check(l.mbx_conv_wgrad_scaled(C.byref(d), dyg.data_ptr(), rows * ld, ld, 1.0, dw.data_ptr(), db.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        assert torch.equal(dw.cpu(), ref_w), "dw tile_config %d: %d elements differ" % (cfg, int((dw.cpu() != ref_w).sum()))
+        assert torch.equal(db.cpu(), ref_b), "db tile_config %d" % cfg
+
+
 # ------------------------------------------------------------------------------------------------ (b) grouped weight gradient
 @pytest.mark.parametrize("flags", [0, 1, 2], ids=["default", "deterministic", "scatter"])
 @pytest.mark.parametrize("plan", ["A", "B"])

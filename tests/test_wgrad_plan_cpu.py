@@ -15,7 +15,7 @@ class _Item(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("layer", "tile_n", "tile_k", "m_begin", "m_end", "single", "cfg", "p2")]
 
 
-# tile shapes of the grouped launch, in 64-channel / 64-column sub-images (kWgCfgs in csrc/conv.hip)
+# tile shapes of the grouped launch, in 64-channel / 64-column sub-images (kWgCfgs in csrc/wgrad.hip)
 WG_CFGS = [(1, 4), (1, 5), (2, 2), (2, 3), (2, 4), (3, 2), (3, 3)]
 
 

@@ -44,7 +44,7 @@ class Item(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("layer", "tile_n", "tile_k", "m_begin", "m_end", "single", "cfg", "p2")]
 
 
-WG = [(1, 4), (1, 5), (2, 2), (2, 3), (2, 4), (3, 2), (3, 3)]      # kWgCfgs (csrc/conv.hip)
+WG = [(1, 4), (1, 5), (2, 2), (2, 3), (2, 4), (3, 2), (3, 3)]      # kWgCfgs (csrc/wgrad.hip)
 
 
 def timeit(fn):

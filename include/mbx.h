@@ -159,6 +159,46 @@ int mbx_loss_fwd_bwd_mined(const float* decoded /*[B,P,4]*/, const float* conf_i
                            int neg_per_pos, int min_neg, int32_t* n_neg /*[B] or NULL*/,
                            void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
+/* mbx_loss_fwd_bwd with the FOCAL LOSS on the confidence term (Lin et al. 2017, "Focal Loss for Dense Object Detection";
+ * optional, not in the reference, off unless the caller asks): every prior stays in the loss and the well-classified ones are
+ * down-weighted by (1 - p_t)^gamma, with a class weight on each side.  Every argument up to d_logits is mbx_loss_fwd_bwd's,
+ * same order and meaning.  Per prior, in float32 and in mbx_loss_fwd_bwd's operation order:
+ *   s = sigmoid(conf_in) when conf_is_logit, else conf_in;   c = s + 1e-10f;   w = (1 - c) + 1e-10f
+ *   ds = s (1 - s) when conf_is_logit, else 1
+ * and then
+ *   positive (match >= 0):  term L = -w_pos * w^gamma * log c     dL/ds = w_pos * (gamma * w^(gamma-1) * log c - w^gamma / c)
+ *   counted negative:       term L = -w_neg * c^gamma * log w     dL/ds = w_neg * (c^gamma / w - gamma * c^(gamma-1) * log w)
+ *   d_logits = dL/ds * ds * grad_scale;   loss2[1] = the sum of the terms, accumulated in double.
+ * With gamma == 0 the gamma * x^(gamma-1) * log term is left out, not multiplied by zero.  Both gradient brackets are sums
+ * of same-sign terms: nothing cancels.  With s exactly 0 or 1 the epsilons keep c, w >= 1e-10, so every term and gradient
+ * is finite for gamma in [0, 10], gamma < 1 included.  The paper's alpha is w_pos = alpha, w_neg = 1 - alpha (0.25 with
+ * gamma = 2).  The location loss, d_raw_locs and loss2[0] are mbx_loss_fwd_bwd's, untouched.  Nothing is normalised by
+ * the number of positives: the loss stays a batch sum and grad_scale the caller's.  A conf_in outside [0, 1] with
+ * conf_is_logit = 0, or a NaN, gives whatever IEEE arithmetic gives, as in mbx_loss_fwd_bwd.
+ * Which negatives are counted:
+ *   neg_per_pos == 0: every negative; min_neg must be 0; n_neg[b] = P - n_pos (n_neg may be NULL).
+ *   neg_per_pos >= 1: exactly the selection of mbx_loss_fwd_bwd_mined -- the same key on conf_in, the same K, the same
+ *   ties, n_neg[b] = K.  The focal negative term is increasing in c, so the highest score is still the highest loss.  An
+ *   unselected negative adds nothing to conf_loss and its d_logits is +0.0f.
+ * gamma == 0 && w_pos == 1 && w_neg == 1 gives loss2, d_raw_locs and d_logits byte-identical to mbx_loss_fwd_bwd
+ * (neg_per_pos == 0) and to mbx_loss_fwd_bwd_mined with the same neg_per_pos / min_neg (neg_per_pos >= 1): same per-thread
+ * stride, same reduction order, and x * 1.0f is exact.  An image's outputs depend on its own row only -- not on B or its
+ * place in the launch -- and the same input gives the same bytes on every call (no floating-point atomics).  Any P.
+ * gamma not in [0, 10] (NaN included), a weight that is negative or not finite, neg_per_pos < 0, min_neg < 0, min_neg > 0
+ * with neg_per_pos == 0, or anything mbx_loss_fwd_bwd rejects: MBX_ERR_INVALID_ARG; workspace_bytes <
+ * mbx_loss_focal_workspace_bytes(B, P): MBX_ERR_WORKSPACE; nothing is launched or written either way.  Two launches on
+ * `stream`, one workgroup per image, graph-capturable.
+ * What the focal loss does to AP on real data is NOT measured here: no trained model or dataset is at hand.            */
+size_t mbx_loss_focal_workspace_bytes(int B, int P);
+int mbx_loss_fwd_bwd_focal(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B,P]*/,
+                           int conf_is_logit, const float* gt /*[B,G,4]*/,
+                           const int32_t* match /*[B,P]*/, float alpha, float grad_scale, int B, int P,
+                           int G, float* loss2 /*[2]*/,
+                           float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
+                           float gamma, float w_pos, float w_neg,
+                           int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
+                           void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
 /* ------------------------------------------------- detect post-processing (A9-A12)
  * Replaces the per-patch numpy loop detect.py:408-436: decode + clip [0,1]
  * (412-413), filter_proposals (74-104, strict inequalities), sort by confidence

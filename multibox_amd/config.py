@@ -82,3 +82,22 @@ def match_iou_threshold(cfg):
     if not (isinstance(v, (int, float)) and not isinstance(v, bool) and 0 < v <= 1):
         raise ValueError("LOSS_MATCH_IOU_THRESHOLD must be a number in (0, 1], got %r" % (v,))
     return float(v)
+
+
+def focal_loss(cfg):
+    """Focal loss on the confidence term (mbx_loss_fwd_bwd_focal; not in the reference, so off when absent): None, or
+    (gamma, alpha_or_None) from LOSS_FOCAL_GAMMA (a number in [0, 10]; absent or null = off) and LOSS_FOCAL_ALPHA (a number
+    strictly inside (0, 1), default null = both sides weigh 1; only with LOSS_FOCAL_GAMMA).  Alpha weighs the positives and
+    1 - alpha the negatives, the paper's convention (0.25 with gamma = 2).  A bool, a string, a list, a NaN or a value
+    out of range raises ValueError naming the key.  Host code only."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    gamma, alpha = cfg.get("LOSS_FOCAL_GAMMA"), cfg.get("LOSS_FOCAL_ALPHA")
+    if gamma is None:
+        if alpha is not None:
+            raise ValueError("LOSS_FOCAL_ALPHA is given without LOSS_FOCAL_GAMMA")
+        return None
+    if not (number(gamma) and 0 <= gamma <= 10):
+        raise ValueError("LOSS_FOCAL_GAMMA must be a number in [0, 10], got %r" % (gamma,))
+    if alpha is not None and not (number(alpha) and 0 < alpha < 1):
+        raise ValueError("LOSS_FOCAL_ALPHA must be a number inside (0, 1), got %r" % (alpha,))
+    return float(gamma), (None if alpha is None else float(alpha))

@@ -324,27 +324,22 @@ __device__ __forceinline__ unsigned long long mined_key(float conf_in, int P, in
   return ((unsigned long long)score_order_key(conf_in) << 32) | (unsigned)(P - 1 - p);
 }
 
-// loss_kernel with only the K highest-ranked negatives of each image counted (mbx_loss_fwd_bwd_mined, mbx.h).  One
-// workgroup per image.  The K-th largest composite key -- the cut -- is found by a radix select: per 8-bit digit, most
-// significant first, a 256-bin LDS histogram of the candidates that still share the digits fixed so far, then one wave
+// The cut of hard-negative mining for image b: the K-th largest composite key among its negatives, K as in mbx.h
+// (mbx_loss_fwd_bwd_mined); a negative is selected iff its key is >= the cut.  Called by every thread of a workgroup of
+// kThreads (loss_mined_kernel, loss_focal_kernel).  Found by a radix select: per 8-bit digit, most significant
+// first, a 256-bin LDS histogram of the candidates that still share the digits fixed so far, then one wave
 // walks the bins from the top to the one that holds the K-th.  No sort, nothing held per thread: any P.  A pass re-reads
 // the row (2.6-26 KB: L1 / L2 hits).  The select ends as soon as the bin it lands in is taken whole (its count is what is
 // still needed): with distinct scores that is after 3-4 passes, and at once when K is 0 or every negative is taken.  Index
-// digits above the bits of P-1 are zero for every candidate and are skipped.  The last pass is loss_kernel's loop, same
-// stride, same reduction, with "negative and below the cut -> no loss, +0 gradient": byte-identical to it when all are taken.
-__global__ void __launch_bounds__(kThreads)
-loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
-                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
-                  int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
-                  float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+// digits above the bits of P-1 are zero for every candidate and are skipped.  K goes to n_neg[b] (n_neg may be null).
+__device__ __forceinline__ unsigned long long mined_select_cut(const int* __restrict__ mt, const float* __restrict__ cf,
+                                                               int P, int neg_per_pos, int min_neg, int b,
+                                                               int* __restrict__ n_neg) {
   static_assert(kThreads == 256, "one thread per histogram bin, four bins per lane of the walking wave");
   __shared__ unsigned hist[256];
   __shared__ unsigned long long sh_cut;
   __shared__ int sh_need, sh_done;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int* mt = match + (size_t)b * P;
-  const float* cf = logits + (size_t)b * P;
-
+  const int tid = threadIdx.x;
   unsigned long long cut = 0ull;     // the digits fixed so far, zeros below
   int need = 0;                      // candidates still to take among those that share them
   for (int shift = 56; shift >= 0; shift -= 8) {
@@ -397,6 +392,20 @@ loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
     need = sh_need;
     if (sh_done) break;
   }
+  return cut;
+}
+
+// loss_kernel with only the K highest-ranked negatives of each image counted (mbx_loss_fwd_bwd_mined, mbx.h).  One
+// workgroup per image.  After the select (mined_select_cut) the pass is loss_kernel's loop, same stride, same
+// reduction, with "negative and below the cut -> no loss, +0 gradient": byte-identical to it when all are taken.
+__global__ void __launch_bounds__(kThreads)
+loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                  int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
+                  float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const unsigned long long cut = mined_select_cut(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg,
+                                                  b, n_neg);
 
   double loc_acc = 0.0, conf_acc = 0.0;
   for (int p = tid; p < P; p += kThreads) {
@@ -440,6 +449,84 @@ loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
     for (int w = 0; w < kWaves; ++w) { a += red[w][0]; c += red[w][1]; }
     partial[2 * b] = a;
     partial[2 * b + 1] = c;
+  }
+}
+
+// ------------------------------------------------------------------ focal loss
+// loss_kernel with the confidence terms of the focal loss (mbx_loss_fwd_bwd_focal, mbx.h): a positive's -log c is weighted
+// by w_pos * w^gamma, a counted negative's -log w by w_neg * c^gamma.  MINED: only the negatives at or over
+// mined_select_cut's cut count, as in loss_mined_kernel.  One workgroup per image, loss_kernel's stride and reduction.
+// One powf per prior on top of loss_kernel's expf / logf (x^(gamma-1) is x^gamma / x); the term is formed in double from
+// the float32 power and logarithm, the gradient in float32.  With gamma == 0 the power is the constant 1 and the
+// gamma * x^(gamma-1) * log term is left out, so with unit weights every product below is `x * 1.0f` and the bytes are
+// loss_kernel's (loss_mined_kernel's when MINED): the file is built with -ffp-contract=off.
+template <bool MINED>
+__global__ void __launch_bounds__(kThreads)
+loss_focal_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                  int P, int G, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
+                  double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs, float* __restrict__ d_logits,
+                  int* __restrict__ n_neg) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  unsigned long long cut = 0ull;                             // no key is below 0: every negative counts
+  if (MINED) cut = mined_select_cut(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg, b, n_neg);
+  const bool modulated = gamma != 0.0f;
+
+  double loc_acc = 0.0, conf_acc = 0.0;
+  int n_pos = 0;
+  for (int p = tid; p < P; p += kThreads) {
+    const size_t i = (size_t)b * P + p;
+    const int m = match[i];
+    const float z = logits[i];
+    float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
+    float g;
+    if (MINED && m < 0 && mined_key(z, P, p) < cut) {
+      g = 0.f;                                              // an unselected negative: no loss, +0 whatever grad_scale is
+    } else {
+      const float s = is_logit ? 1.0f / (1.0f + expf(-z)) : z;
+      const float c = __fadd_rn(s, 1e-10f);                  // loss.py:74
+      const float w = __fadd_rn(__fsub_rn(1.0f, c), 1e-10f);
+      const float ds = is_logit ? s * (1.0f - s) : 1.0f;
+      const bool pos = m >= 0;
+      if (pos) {
+        const float4 l = decoded[i], q = gt[(size_t)b * G + m];
+        const float d0 = __fsub_rn(l.x, q.x), d1 = __fsub_rn(l.y, q.y), d2 = __fsub_rn(l.z, q.z), d3 = __fsub_rn(l.w, q.w);
+        loc_acc += (double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2 + (double)d3 * d3;   // loss.py:100
+        const float a = alpha * grad_scale;
+        dl = make_float4(a * d0, a * d1, a * d2, a * d3);
+        ++n_pos;
+      }
+      // The two sides are one expression with c and w exchanged, -wt * base^gamma * log(arg): one logf and one powf for
+      // a wavefront that holds positives and negatives, not one of each per side.
+      const float arg = pos ? c : w, base = pos ? w : c, wt = pos ? w_pos : w_neg;
+      const float lg = logf(arg);
+      const float pw = modulated ? powf(base, gamma) : 1.0f;
+      conf_acc -= (double)wt * ((double)pw * (double)lg);
+      float d = (ds * pw) / arg;
+      if (modulated) d = d - gamma * (pw / base) * lg * ds;               // lg <= 0: both terms are >= 0, no cancellation
+      d = wt * d;
+      g = (pos ? -d : d) * grad_scale;
+    }
+    if (d_locs) d_locs[i] = dl;
+    if (d_logits) d_logits[i] = g;
+  }
+  loc_acc = wave_sum(loc_acc);
+  conf_acc = wave_sum(conf_acc);
+  __shared__ double red[kWaves][2];
+  __shared__ int pos_waves[kWaves];
+  if (!MINED) n_pos = wave_sum(n_pos);
+  if ((tid & 63) == 0) { red[tid >> 6][0] = loc_acc; red[tid >> 6][1] = conf_acc; pos_waves[tid >> 6] = n_pos; }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, c = 0.0;
+    for (int w = 0; w < kWaves; ++w) { a += red[w][0]; c += red[w][1]; }
+    partial[2 * b] = a;
+    partial[2 * b + 1] = c;
+    if (!MINED && n_neg) {                                   // every negative counts
+      int total = 0;
+      for (int w = 0; w < kWaves; ++w) total += pos_waves[w];
+      n_neg[b] = P - total;
+    }
   }
 }
 
@@ -608,6 +695,31 @@ extern "C" int mbx_loss_fwd_bwd_mined(const float* decoded, const float* logits,
                      reinterpret_cast<const float4*>(decoded), logits, conf_is_logit,
                      reinterpret_cast<const float4*>(gt), match, alpha, grad_scale, P, G, neg_per_pos, min_neg, partial,
                      reinterpret_cast<float4*>(d_raw_locs), d_logits, n_neg);
+  MBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" size_t mbx_loss_focal_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+
+extern "C" int mbx_loss_fwd_bwd_focal(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                      const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                      float* d_raw_locs, float* d_logits, float gamma, float w_pos, float w_neg,
+                                      int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes,
+                                      mbx_stream_t stream) {
+  if (!decoded || !logits || !gt || !match || !loss2 || B <= 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (!(gamma >= 0.0f && gamma <= 10.0f)) return MBX_ERR_INVALID_ARG;                      // a NaN fails both
+  if (!(w_pos >= 0.0f && w_neg >= 0.0f) || isinf(w_pos) || isinf(w_neg)) return MBX_ERR_INVALID_ARG;
+  if (neg_per_pos < 0 || min_neg < 0 || (neg_per_pos == 0 && min_neg > 0)) return MBX_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < mbx_loss_focal_workspace_bytes(B, P)) return MBX_ERR_WORKSPACE;
+  double* partial = reinterpret_cast<double*>(workspace);
+  MBX_ENTER();
+  const auto kernel = neg_per_pos ? loss_focal_kernel<true> : loss_focal_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream),
+                     reinterpret_cast<const float4*>(decoded), logits, conf_is_logit,
+                     reinterpret_cast<const float4*>(gt), match, alpha, grad_scale, P, G, gamma, w_pos, w_neg, neg_per_pos,
+                     min_neg, partial, reinterpret_cast<float4*>(d_raw_locs), d_logits, n_neg);
   MBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
   MBX_LAUNCH_CHECK();

@@ -76,6 +76,22 @@ def compute_assignments(locations, confidences, gt_bboxes, num_gt_bboxes, batch_
     return [part, stacked]
 
 
+def _focal_arguments(focal_gamma, focal_alpha):
+    """None (off), or (gamma, w_pos, w_neg) as mbx_loss_fwd_bwd_focal takes them.  Raises ValueError on a bad value."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if focal_gamma is None:
+        if focal_alpha is not None:
+            raise ValueError("focal_alpha is given without focal_gamma")
+        return None
+    if not (number(focal_gamma) and 0.0 <= focal_gamma <= 10.0):
+        raise ValueError("focal_gamma must be a number in [0, 10], got %r" % (focal_gamma,))
+    if focal_alpha is None:
+        return float(focal_gamma), 1.0, 1.0
+    if not (number(focal_alpha) and 0.0 < focal_alpha < 1.0):
+        raise ValueError("focal_alpha must be a number inside (0, 1), got %r" % (focal_alpha,))
+    return float(focal_gamma), float(focal_alpha), 1.0 - float(focal_alpha)
+
+
 class MultiboxLoss:
     """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step).
 
@@ -86,10 +102,17 @@ class MultiboxLoss:
     match_iou_threshold (a float in (0, 1]; None = off, the reference's bipartite match alone): threshold matching --
     behind mbx_match every prior still free goes to the box it overlaps most if that IoU is over the threshold
     (mbx_match_extend, include/mbx.h); the number added per image is left in ``n_extra``.  The loss, mined or not, reads
-    the extended ``match``.  What that does to AP on real data is not measured here either."""
+    the extended ``match``.  What that does to AP on real data is not measured here either.
+
+    focal_gamma (a float in [0, 10]; None = off, the reference's loss): the focal loss on the confidence term -- a
+    positive's -log c is weighted by w^gamma and a counted negative's -log w by c^gamma (mbx_loss_fwd_bwd_focal,
+    include/mbx.h).  focal_alpha (a float inside (0, 1); None = both sides weigh 1; only with focal_gamma) weighs the
+    positives by alpha and the negatives by 1 - alpha.  With neg_per_pos the mined negatives are the ones counted, and the
+    extended ``match`` is read as by the other two.  What that does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
-                 min_neg=0, match_iou_threshold=None):
+                 min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None):
+        self.focal = _focal_arguments(focal_gamma, focal_alpha)
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
         self.P = self.priors.shape[0]
         self.B, self.G, self.alpha = int(batch_size), int(max_num_bboxes), float(location_loss_alpha)
@@ -106,6 +129,8 @@ class MultiboxLoss:
         if neg_per_pos is not None:
             self.n_neg = torch.zeros((self.B,), dtype=torch.int32, device=device)
             ws_bytes = _lib.lib().mbx_loss_mined_workspace_bytes(self.B, self.P)
+        if self.focal is not None:
+            ws_bytes = _lib.lib().mbx_loss_focal_workspace_bytes(self.B, self.P)
         self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
         self.match_iou_threshold, self.n_extra = match_iou_threshold, None
         if match_iou_threshold is not None:
@@ -134,7 +159,17 @@ class MultiboxLoss:
             _lib.check(l.mbx_match_extend(self.priors.data_ptr(), gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),
                                           self.status.data_ptr(), self.match_iou_threshold, B, P, G,
                                           self.match.data_ptr(), self.n_extra.data_ptr(), s), "mbx_match_extend")
-        if self.neg_per_pos is None:
+        if self.focal is not None:
+            gamma, w_pos, w_neg = self.focal
+            mined = self.neg_per_pos is not None
+            _lib.check(l.mbx_loss_fwd_bwd_focal(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
+                                                gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
+                                                B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
+                                                self.d_logits.data_ptr(), gamma, w_pos, w_neg,
+                                                self.neg_per_pos if mined else 0, self.min_neg if mined else 0,
+                                                self.n_neg.data_ptr() if mined else None, self.ws.data_ptr(),
+                                                self.ws.numel(), s), "mbx_loss_fwd_bwd_focal")
+        elif self.neg_per_pos is None:
             _lib.check(l.mbx_loss_fwd_bwd(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
                                           gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
                                           B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(), self.d_logits.data_ptr(),

@@ -1,15 +1,18 @@
-"""mbx_loss_fwd_bwd against mbx_loss_fwd_bwd_mined (hard-negative mining, neg_per_pos = 3) at the headline shape (64 images,
-P = 646, G = 13) and the 512x512 shape (P = 3199, G = 100): what the selection costs on top of the loss it feeds.
+"""mbx_loss_fwd_bwd against mbx_loss_fwd_bwd_mined (hard-negative mining, neg_per_pos = 3) and mbx_loss_fwd_bwd_focal (the
+focal loss, gamma = 2, alpha = 0.25, without mining and with neg_per_pos = 3) at the headline shape (64 images, P = 646,
+G = 13) and the 512x512 shape (P = 3199, G = 100): what the selection, and the power per prior, cost on top of the loss.
 
-Both entry points run in one process on the same buffers.  A call is two launches of a few microseconds, so a host loop
-would time the enqueue: CALLS calls of each are captured into a graph of their own, both graphs are warmed up, then
+The entry points run in one process on the same buffers.  A call is two launches of a few microseconds, so a host loop
+would time the enqueue: CALLS calls of each are captured into a graph of their own, the graphs are warmed up, then
 replayed alternately for ROUNDS rounds, each replay between a pair of device events.  Reported: the median time per call
-and its range over the rounds, and the ratio of the medians.  What mining does to AP is not measured: that needs a dataset.
+and its range over the rounds, and the ratios of the medians (focal against unmined, focal_mined against mined: the same
+selection).  What mining or the focal loss do to AP is not measured: that needs a dataset.
 usage: python tools/loss_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CALLS, ROUNDS, NEG_PER_POS = 2000, 15, 3
+FOCAL_GAMMA, FOCAL_ALPHA = 2.0, 0.25
 
 if __name__ == "__main__":
     import numpy as np, torch
@@ -31,7 +34,8 @@ if __name__ == "__main__":
         f = dict(dtype=torch.float32, device="cuda")
         loss2, dl, dz = torch.zeros(2, **f), torch.zeros(B, P, 4, **f), torch.zeros(B, P, **f)
         n_neg = torch.zeros(B, dtype=torch.int32, device="cuda")
-        ws = torch.empty(max(l.mbx_loss_workspace_bytes(B), l.mbx_loss_mined_workspace_bytes(B, P)), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(l.mbx_loss_workspace_bytes(B), l.mbx_loss_mined_workspace_bytes(B, P),
+                             l.mbx_loss_focal_workspace_bytes(B, P)), dtype=torch.uint8, device="cuda")
         head = (dec.data_ptr(), logits.data_ptr(), 1, gt.data_ptr(), match.data_ptr(), 1000.0, 1.0, B, P, G, loss2.data_ptr(),
                 dl.data_ptr(), dz.data_ptr())
         tail = (ws.data_ptr(), ws.numel())
@@ -42,8 +46,13 @@ if __name__ == "__main__":
         def mined():
             _lib.check(l.mbx_loss_fwd_bwd_mined(*head, NEG_PER_POS, 0, n_neg.data_ptr(), *tail,
                                                 torch.cuda.current_stream().cuda_stream), "mbx_loss_fwd_bwd_mined")
+
+        def focal(neg_per_pos=0):
+            _lib.check(l.mbx_loss_fwd_bwd_focal(*head, FOCAL_GAMMA, FOCAL_ALPHA, 1.0 - FOCAL_ALPHA, neg_per_pos, 0,
+                                                n_neg.data_ptr(), *tail, torch.cuda.current_stream().cuda_stream),
+                       "mbx_loss_fwd_bwd_focal")
         graphs = {}
-        for name, fn in (("unmined", plain), ("mined", mined)):
+        for name, fn in (("unmined", plain), ("mined", mined), ("focal", focal), ("focal_mined", lambda: focal(NEG_PER_POS))):
             fn()                                               # lazy code-object load, outside the capture
             torch.cuda.synchronize()
             graphs[name] = torch.cuda.CUDAGraph()
@@ -53,6 +62,7 @@ if __name__ == "__main__":
         for _ in range(3):
             for gr in graphs.values():
                 gr.replay()
+        mined()                                                # n_neg as the mined entry leaves it
         torch.cuda.synchronize()
         kept = n_neg.float().mean().item()
         times = {name: [] for name in graphs}
@@ -67,5 +77,7 @@ if __name__ == "__main__":
         med = {name: float(np.median(t)) for name, t in times.items()}
         print("B=%d P=%d G=%d neg_per_pos=%d (%.1f of %.1f negatives kept per image): " % (B, P, G, NEG_PER_POS, kept, P - n_pos.mean())
               + "  ".join("%s %.2f us (%.2f..%.2f)" % (name, med[name], min(t), max(t)) for name, t in times.items())
-              + "  mined / unmined = %.2f  [median of %d graph replays of %d calls each, alternating]" % (
-                  med["mined"] / med["unmined"], ROUNDS, CALLS), flush=True)
+              + "  mined / unmined = %.2f  focal / unmined = %.2f  focal_mined / mined = %.2f  [focal: gamma = %g, alpha = %g; "
+                "median of %d graph replays of %d calls each, alternating]" % (
+                  med["mined"] / med["unmined"], med["focal"] / med["unmined"], med["focal_mined"] / med["mined"],
+                  FOCAL_GAMMA, FOCAL_ALPHA, ROUNDS, CALLS), flush=True)

@@ -41,7 +41,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -66,6 +66,7 @@ def main():
     try:                                          # [new] LOSS_NEG_PER_POS / LOSS_MIN_NEG: hard-negative mining, off when absent
         mining = negative_mining(cfg)
         match_iou = match_iou_threshold(cfg)      # [new] LOSS_MATCH_IOU_THRESHOLD: threshold matching, off when absent
+        focal = focal_loss(cfg)                   # [new] LOSS_FOCAL_GAMMA / LOSS_FOCAL_ALPHA: focal loss, off when absent
     except ValueError as e:
         raise SystemExit("config: %s" % e)
     torch.cuda.set_device(local_rank)
@@ -88,7 +89,8 @@ def main():
                  rmsprop_decay=cfg.RMSPROP_DECAY, rmsprop_momentum=float(cfg.RMSPROP_MOMENTUM), rmsprop_epsilon=cfg.RMSPROP_EPSILON,
                  moving_average_decay=cfg.MOVING_AVERAGE_DECAY, process_group=pg, trainable_scopes=args.trainable_scopes,
                  neg_per_pos=mining[0] if mining else None, min_neg=mining[1] if mining else 0,
-                 match_iou_threshold=match_iou)
+                 match_iou_threshold=match_iou, focal_gamma=focal[0] if focal else None,
+                 focal_alpha=focal[1] if focal else None)
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -179,6 +181,8 @@ def main():
                 rec["mined_negatives_per_image"] = tr.mined_negatives_per_image()
             if match_iou is not None:
                 rec["extra_matches_per_image"] = tr.extra_matches_per_image()
+            if focal:
+                rec["focal_gamma"], rec["focal_alpha"] = focal
             print("global step %d: loss = %.4f (loc %.4f conf %.4f) lr %.6f %.1f img/s" % (tr.global_step, total, loc, conf, tr.lr, ips))
             log.write(json.dumps(rec) + "\n")
             log.flush()

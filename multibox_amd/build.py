@@ -32,6 +32,7 @@ SOURCES = {
     "convd.hip": [],
     "convr.hip": [],
     "nnops.hip": ["-munsafe-fp-atomics"],
+    "bn.hip": ["-munsafe-fp-atomics"],
     "augment.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function"]

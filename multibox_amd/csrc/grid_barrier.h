@@ -1,6 +1,6 @@
 // ONE-SHOT GRID BARRIER shared by the launches that keep a grid-wide dependency inside the kernel (round 6): the convolution +
 // batch-norm-apply launch (fused_bn.h) and the data-gradient + batch-norm-backward launch.  The protocol is the one
-// bn_bwd_onepass_kernel (nnops.hip) has run since round 2 and the saturation stress test covers: everything that is polled or
+// bn_bwd_onepass_kernel (bn.hip) has run since round 2 and the saturation stress test covers: everything that is polled or
 // counted sits on its own 128-byte line and is shared by few workgroups (a device-scope atomic or load is served at the memory
 // side at ~24 ns per access and line: tools/atomic_bench.hip) -- arrivals go to kGbSub counters, the last arrival of each to
 // the top counter, the last of those sets kGbRel release words; workgroup b polls release word b % kGbRel.

@@ -100,6 +100,49 @@ def test_bn_forward_backward(T, M, Cc, relu):
     assert torch.equal(av2.tensor(), av.tensor()) and torch.equal(dm2, dm) and torch.equal(dr2, dr)
     assert torch.equal(mm2, mm) and torch.equal(mv2, mv)
 
+
+@pytest.mark.parametrize("M,Cc", [(300, 8), (1001, 24), (37, 2056)])
+def test_bn_apply_edge_shapes(T, M, Cc):
+    """The forward apply where its lane geometry is awkward: one channel group (256 rows per sweep, M ragged against it),
+    three channel groups (thread 255 idle, 85 rows per sweep), and more channel groups than threads (C / 8 = 257: the
+    generic walk of bn_apply_kernel).  Reference and tolerances of test_bn_forward_backward; the activation is a strided
+    view (ld_a > C) whose padding columns must stay as they were.  Where the fused form takes its one-launch path (the
+    first two shapes) it gives the same bytes."""
+    torch = T
+    from multibox_amd import _lib
+    l = _lib.lib()
+    gen = torch.Generator().manual_seed(M + Cc)
+    y = bfr(torch, torch.randn(M, Cc, generator=gen) * 2 + 0.5)
+    beta = torch.randn(Cc, generator=gen) * 0.3
+    mean, var = y.mean(0), y.var(0, unbiased=False)
+    h = M // 2
+    part = torch.stack([torch.stack([y[:h].sum(0), (y[:h] ** 2).sum(0)], 1), torch.stack([y[h:].sum(0), (y[h:] ** 2).sum(0)], 1)]).cuda().contiguous()
+    dm, dr = torch.zeros(Cc, device="cuda"), torch.zeros(Cc, device="cuda")
+    mm, mv = torch.zeros(Cc, device="cuda"), torch.ones(Cc, device="cuda")
+    _lib.check(l.mbx_bn_finalize(part.data_ptr(), 2, Cc, M, 0.001, 0.9, dm.data_ptr(), dr.data_ptr(), mm.data_ptr(), mv.data_ptr(), S()))
+    assert torch.allclose(dm.cpu(), mean, rtol=1e-4, atol=1e-5)
+    assert torch.allclose(dr.cpu(), torch.rsqrt(var + 0.001), rtol=1e-4)
+    yd, bd = y.to(torch.bfloat16).cuda(), beta.cuda()
+    off, ld, guard = 8, Cc + 24, 7.0                          # 8 padding columns in front of the view, 16 behind
+    for relu in (1, 0):
+        a_ref = (y - mean) * torch.rsqrt(var + 0.001) + beta
+        if relu:
+            a_ref = torch.relu(a_ref)
+        buf = torch.full((M, ld), guard, dtype=torch.bfloat16, device="cuda")
+        _lib.check(l.mbx_bn_apply(yd.data_ptr(), M, Cc, dm.data_ptr(), dr.data_ptr(), bd.data_ptr(), relu, buf.data_ptr() + 2 * off, ld, S()))
+        ok, msg = close_bf16(buf[:, off:off + Cc], a_ref)
+        assert ok, "bn_apply relu=%d: %s" % (relu, msg)
+        assert bool((buf[:, :off] == guard).all()) and bool((buf[:, off + Cc:] == guard).all()), "padding written (relu=%d)" % relu
+        if Cc > 2048:                                         # (wider than any layer: only the plain apply is asked to take it)
+            continue
+        buf2 = torch.full((M, ld), guard, dtype=torch.bfloat16, device="cuda")
+        dm2, dr2 = torch.zeros(Cc, device="cuda"), torch.zeros(Cc, device="cuda")
+        mm2, mv2 = torch.zeros(Cc, device="cuda"), torch.ones(Cc, device="cuda")
+        _lib.check(l.mbx_bn_apply_fused(part.data_ptr(), 2, M, 0.001, 0.9, yd.data_ptr(), M, Cc, bd.data_ptr(), relu, buf2.data_ptr() + 2 * off, ld,
+                                        dm2.data_ptr(), dr2.data_ptr(), mm2.data_ptr(), mv2.data_ptr(), S()))
+        assert torch.equal(buf2, buf) and torch.equal(dm2, dm) and torch.equal(dr2, dr)
+        assert torch.equal(mm2, mm) and torch.equal(mv2, mv)
+
 @pytest.mark.parametrize("M,Cc,relu", [(2450, 96, 1), (18496, 160, 1), (18496, 320, 1), (78400, 96, 1), (18496, 512, 0),
                                        (18496, 768, 1), (78400, 208, 1), (78400, 256, 1), (4096, 1536, 1), (1001, 24, 1),
                                        (7, 8, 0)])

@@ -19,6 +19,7 @@ ARCH = "gfx950"
 # source -> extra flags.  -ffp-contract=off where float rounding sequence is part of parity.
 SOURCES = {
     "priors.cpp": ["-ffp-contract=off"],
+    "loss.hip": ["-ffp-contract=off"],
     "postproc.hip": ["-ffp-contract=off"],
     "merge.hip": ["-ffp-contract=off"],
     "cocomatch.hip": ["-ffp-contract=off"],

@@ -1,5 +1,6 @@
-// Device helpers shared by the detection post-processing kernels (postproc.hip: top-K and per-patch NMS; merge.hip: the
-// per-image merge and box voting).  Keep decisions are compared bit for bit with the numpy restatements, so both files are
+// Device helpers shared by the box kernels: detection post-processing (postproc.hip: top-K and per-patch NMS; merge.hip: the
+// per-image merge and box voting) and the training side (loss.hip: threshold matching takes Box / box_area, the mining keys
+// score_order_key).  Keep decisions are compared bit for bit with the numpy restatements, so these files are
 // built with -ffp-contract=off and the float64 IoU below keeps the operation order of oracle.ref_numpy.nms_greedy.
 // (cocomatch.hip's IoU is NOT this one: the xywh form of the host's _iou_xywh, with its own term order.)
 #pragma once

@@ -1,0 +1,601 @@
+// libmbx: the training side of the box arithmetic -- prior decode, bipartite matching, threshold matching, loss fwd+bwd
+// (plain, with hard-negative mining, focal).  The detection side is postproc.hip.
+// HBM/latency-bound integer+float kernels; one workgroup per image,
+// wave64 shuffle reductions.  Built with -ffp-contract=off: the float32 cost arithmetic
+// must keep the reference's rounding sequence (loss.py:21-35).
+#include "boxes.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+
+// ------------------------------------------------------------------ decode + conf
+__global__ void __launch_bounds__(kThreads)
+decode_conf_kernel(const float4* __restrict__ raw, const float* __restrict__ logits,
+                   const float4* __restrict__ priors, int total, int P, float eps_add,
+                   float4* __restrict__ decoded, float* __restrict__ conf) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    if (decoded) {
+      const float4 r = raw[i], p = priors[i % P];
+      decoded[i] = make_float4(__fadd_rn(r.x, p.x), __fadd_rn(r.y, p.y), __fadd_rn(r.z, p.z), __fadd_rn(r.w, p.w));
+    }
+    if (conf) {
+      const float s = 1.0f / (1.0f + expf(-logits[i]));     // model.py:322
+      conf[i] = __fadd_rn(s, eps_add);                      // loss.py:74
+    }
+  }
+}
+
+// ----------------------------------------------------------------------- matching
+// cost of (prediction, gt) in the reference's float32 operation order, loss.py:35:
+//   (alpha/2) * norm(l - g)**2 - log c + log(1-c)          (left to right)
+__device__ __forceinline__ double match_cost(const float4 l, const float4 g, float half_alpha,
+                                             float lc, float l1c) {
+  const float d0 = __fsub_rn(l.x, g.x), d1 = __fsub_rn(l.y, g.y), d2 = __fsub_rn(l.z, g.z), d3 = __fsub_rn(l.w, g.w);
+  const float ss = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)), __fmul_rn(d3, d3));
+  const float nrm = __fsqrt_rn(ss);
+  float t = __fmul_rn(half_alpha, __fmul_rn(nrm, nrm));
+  t = __fsub_rn(t, lc);
+  t = __fadd_rn(t, l1c);
+  return (double)t;
+}
+
+struct Cand {
+  double val;
+  int j;      // column (prediction); -1 = none
+  int free_;  // 1 if the column is unassigned
+};
+
+__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
+  if (a.j < 0) return false;
+  if (b.j < 0) return true;
+  if (a.val < b.val) return true;
+  if (a.val > b.val) return false;
+  if (a.free_ != b.free_) return a.free_ > b.free_;   // scipy prefers an unassigned column among equals
+  return a.j < b.j;
+}
+
+__device__ __forceinline__ Cand cand_shfl_xor(const Cand& c, int o) {
+  Cand r;
+  r.val = __shfl_xor(c.val, o, 64);
+  r.j = __shfl_xor(c.j, o, 64);
+  r.free_ = __shfl_xor(c.free_, o, 64);
+  return r;
+}
+
+// One workgroup per image.  Rectangular LSAP on the transposed problem (rows = gt boxes,
+// columns = predictions), shortest augmenting path with float64 duals, as scipy's
+// linear_sum_assignment (loss.py:40).  LDS: 36 B per prediction + 16 B per gt.  256 threads per image up to 1536 predictions,
+// 512 beyond (round 4, tools/match_bench.py on random boxes: P = 3199 / G = 100 812 -> 589 us; P = 646 is fastest at 256:
+// 47 us against 84 with one wave -- the column scan, not the barriers, is what an iteration costs; staging the locations in
+// LDS changed nothing: they are L1 hits).
+__global__ void __launch_bounds__(1024)
+match_kernel(const float4* __restrict__ decoded, const float* __restrict__ conf,
+             const float4* __restrict__ gt, const int* __restrict__ n_gt, float alpha, int P, int G,
+             int* __restrict__ match, int* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* v = reinterpret_cast<double*>(smem);            // [P] column duals
+  double* spc = v + P;                                    // [P] shortest path costs
+  double* u = spc + P;                                    // [G] row duals
+  float2* lcl = reinterpret_cast<float2*>(u + G);         // [P] {log c, log(1-c)}
+  int* path = reinterpret_cast<int*>(lcl + P);            // [P]
+  int* row4col = path + P;                                // [P]
+  int* SC = row4col + P;                                  // [P]
+  int* col4row = SC + P;                                  // [G]
+  int* SR = col4row + G;                                  // [G]
+  __shared__ Cand wave_best[16];
+  __shared__ int sh_i, sh_sink, sh_bad;
+  __shared__ double sh_min;
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nt = (int)blockDim.x, nwaves = nt >> 6;       // 256 or 512 threads (mbx_match)
+  const float4* loc = decoded + (size_t)b * P;
+  const float* cf = conf + (size_t)b * P;
+  const float4* g = gt + (size_t)b * G;
+  int* mt = match + (size_t)b * P;
+  const int n = n_gt[b];
+  const float half_alpha = alpha / 2.0f;
+
+  if (tid == 0) sh_bad = 0;
+  __syncthreads();
+  int bad = 0;
+  for (int j = tid; j < P; j += nt) {
+    mt[j] = -1;
+    const float c = cf[j];
+    const float lc = logf(c);                              // loss.py:21
+    float w = __fsub_rn(1.0f, c);                          // loss.py:22-24
+    if (w > 1.0f) w = 1.0f;
+    if (w <= 0.0f) w = 1e-10f;
+    const float l1c = logf(w);                             // loss.py:25
+    lcl[j] = make_float2(lc, l1c);
+    v[j] = 0.0;
+    row4col[j] = -1;
+    const float4 l = loc[j];
+    if (!(isfinite(lc) && isfinite(l1c) && isfinite(l.x) && isfinite(l.y) && isfinite(l.z) && isfinite(l.w))) bad = 1;
+  }
+  for (int i = tid; i < G; i += nt) {
+    u[i] = 0.0;
+    col4row[i] = -1;
+    if (i < n) {
+      const float4 q = g[i];
+      if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z) && isfinite(q.w))) bad = 1;
+    }
+  }
+  if (bad) sh_bad = 1;
+  __syncthreads();
+  if (n <= 0) { if (tid == 0) status[b] = 0; return; }
+  if (n > P || n > G) { if (tid == 0) status[b] = 1; return; }
+  if (sh_bad) { if (tid == 0) status[b] = 2; return; }
+
+  for (int cur = 0; cur < n; ++cur) {
+    for (int j = tid; j < P; j += nt) { spc[j] = INFINITY; SC[j] = 0; }
+    for (int i = tid; i < n; i += nt) SR[i] = 0;
+    if (tid == 0) { sh_i = cur; sh_sink = -1; sh_min = 0.0; }
+    __syncthreads();
+    while (true) {
+      const int i = sh_i;
+      const double min_val = sh_min;
+      const float4 gi = g[i];
+      const double ui = u[i];
+      Cand best; best.val = INFINITY; best.j = -1; best.free_ = 0;
+      for (int j = tid; j < P; j += nt) {
+        if (SC[j]) continue;
+        const float2 ll = lcl[j];
+        // scipy: r = minVal + cost[i][j] - u[i] - v[j]
+        const double r = ((min_val + match_cost(loc[j], gi, half_alpha, ll.x, ll.y)) - ui) - v[j];
+        double s = spc[j];
+        if (r < s) { path[j] = i; spc[j] = r; s = r; }
+        Cand c; c.val = s; c.j = j; c.free_ = row4col[j] < 0;
+        if (cand_better(c, best)) best = c;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const Cand other = cand_shfl_xor(best, o);
+        if (cand_better(other, best)) best = other;
+      }
+      if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+      __syncthreads();
+      if (tid == 0) {
+        Cand bb = wave_best[0];
+        for (int w = 1; w < nwaves; ++w) if (cand_better(wave_best[w], bb)) bb = wave_best[w];
+        if (bb.j < 0 || !(bb.val < INFINITY)) {
+          sh_sink = -2;                                    // infeasible
+        } else {
+          sh_min = bb.val;
+          SC[bb.j] = 1;
+          SR[i] = 1;
+          const int r4c = row4col[bb.j];
+          if (r4c < 0) sh_sink = bb.j; else sh_i = r4c;
+        }
+      }
+      __syncthreads();
+      if (sh_sink != -1) break;
+    }
+    const int sink = sh_sink;
+    if (sink == -2) { if (tid == 0) status[b] = 2; return; }
+    const double min_val = sh_min;
+    // dual updates
+    for (int i = tid; i < n; i += nt) {
+      if (i == cur) u[i] += min_val;
+      else if (SR[i]) u[i] += min_val - spc[col4row[i]];
+    }
+    for (int j = tid; j < P; j += nt)
+      if (SC[j]) v[j] -= min_val - spc[j];
+    __syncthreads();
+    if (tid == 0) {                                        // augment along the path
+      int j = sink;
+      while (true) {
+        const int i = path[j];
+        row4col[j] = i;
+        const int t = col4row[i];
+        col4row[i] = j;
+        j = t;
+        if (i == cur) break;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += nt) mt[col4row[i]] = i;
+  if (tid == 0) status[b] = 0;
+}
+
+// ------------------------------------------------------------- threshold matching
+// SSD's second matching step behind match_kernel (mbx_match_extend, mbx.h): every prior the bipartite match left free goes
+// to the box it overlaps most, if that IoU is over `thr`.  One workgroup per image, blockDim.x a multiple of 64 (P rounded
+// up, at most 1024).  The image's n boxes and their areas are widened to float64 into LDS once (40 B a box); a thread keeps
+// its prior's box and area in registers and walks the staged boxes, every lane reading the same LDS address (a broadcast).
+// The IoU is iou_corners' (boxes.h), term by term, with the prior as its first box; a pair that does not overlap has IoU 0,
+// which is never over a threshold > 0, so the float64 division is done for overlapping pairs only.  `best` starts at the
+// threshold and moves on a strictly larger IoU: the lowest j among the largest, and only where that is over the threshold.
+struct StagedBox { Box box; double area; };
+
+__global__ void __launch_bounds__(1024)
+match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict__ gt, const int* __restrict__ n_gt,
+                    const int* __restrict__ status, double thr, int P, int G, int* __restrict__ match,
+                    int* __restrict__ n_extra) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  StagedBox* boxes = reinterpret_cast<StagedBox*>(smem);      // [n]
+  __shared__ int added_waves[16];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = (int)blockDim.x;
+  const int n = n_gt[b];
+  if (status[b] != 0 || n <= 0 || n > G) {                    // skipped: the row stays as it is (n > G never has status 0)
+    if (tid == 0 && n_extra) n_extra[b] = 0;
+    return;
+  }
+  for (int j = tid; j < n; j += nt) {
+    const float4 q = gt[(size_t)b * G + j];
+    StagedBox s;
+    s.box = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    s.area = box_area(s.box);
+    boxes[j] = s;
+  }
+  __syncthreads();
+  int* mt = match + (size_t)b * P;
+  int added = 0;
+  for (int p = tid; p < P; p += nt) {
+    if (mt[p] >= 0) continue;                                 // mbx_match's choice stands
+    const float4 q = priors[p];
+    const Box e = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    const double area_e = box_area(e);
+    double best = thr;
+    int best_j = -1;
+    for (int j = 0; j < n; ++j) {
+      const Box g = boxes[j].box;
+      const double iw = fmin(e.x2, g.x2) - fmax(e.x1, g.x1), ih = fmin(e.y2, g.y2) - fmax(e.y1, g.y1);
+      if (iw > 0.0 && ih > 0.0) {
+        const double inter = iw * ih;
+        const double uni = area_e + boxes[j].area - inter;
+        const double iou = uni > 0.0 ? inter / uni : 0.0;
+        if (iou > best) { best = iou; best_j = j; }
+      }
+    }
+    if (best_j >= 0) { mt[p] = best_j; ++added; }
+  }
+  if (!n_extra) return;
+  added = wave_sum(added);
+  if ((tid & 63) == 0) added_waves[tid >> 6] = added;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int w = 0; w < (nt >> 6); ++w) total += added_waves[w];
+    n_extra[b] = total;
+  }
+}
+
+// ---------------------------------------------------------------------- loss
+__global__ void loss_final_kernel(const double* __restrict__ partial, int B, float alpha, float* __restrict__ loss2) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    double a = 0.0, c = 0.0;
+    for (int b = 0; b < B; ++b) { a += partial[2 * b]; c += partial[2 * b + 1]; }
+    loss2[0] = alpha * (float)(a * 0.5);                   // alpha * tf.nn.l2_loss
+    loss2[1] = (float)c;
+  }
+}
+
+// ------------------------------------------------- loss with hard-negative mining
+// Composite key of a negative: the order-preserving image of its input float (score_order_key) above the INVERTED index
+// P-1-p, so that unsigned order = (score descending, p ascending) and no two candidates are equal.
+__device__ __forceinline__ unsigned long long mined_key(float conf_in, int P, int p) {
+  return ((unsigned long long)score_order_key(conf_in) << 32) | (unsigned)(P - 1 - p);
+}
+
+// The cut of hard-negative mining for image b: the K-th largest composite key among its negatives, K as in mbx.h
+// (mbx_loss_fwd_bwd_mined); a negative is selected iff its key is >= the cut.  Called by every thread of a workgroup of
+// kThreads (loss_mined_kernel, loss_focal_kernel).  Found by a radix select: per 8-bit digit, most significant
+// first, a 256-bin LDS histogram of the candidates that still share the digits fixed so far, then one wave
+// walks the bins from the top to the one that holds the K-th.  No sort, nothing held per thread: any P.  A pass re-reads
+// the row (2.6-26 KB: L1 / L2 hits).  The select ends as soon as the bin it lands in is taken whole (its count is what is
+// still needed): with distinct scores that is after 3-4 passes, and at once when K is 0 or every negative is taken.  Index
+// digits above the bits of P-1 are zero for every candidate and are skipped.  K goes to n_neg[b] (n_neg may be null).
+__device__ __forceinline__ unsigned long long mined_select_cut(const int* __restrict__ mt, const float* __restrict__ cf,
+                                                               int P, int neg_per_pos, int min_neg, int b,
+                                                               int* __restrict__ n_neg) {
+  static_assert(kThreads == 256, "one thread per histogram bin, four bins per lane of the walking wave");
+  __shared__ unsigned hist[256];
+  __shared__ unsigned long long sh_cut;
+  __shared__ int sh_need, sh_done;
+  const int tid = threadIdx.x;
+  unsigned long long cut = 0ull;     // the digits fixed so far, zeros below
+  int need = 0;                      // candidates still to take among those that share them
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    if (shift < 32 && ((unsigned)(P - 1) >> shift) == 0) continue;
+    const unsigned long long fixed = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int p = tid; p < P; p += kThreads) {
+      if (mt[p] >= 0) continue;
+      const unsigned long long key = mined_key(cf[p], P, p);
+      if (((key ^ cut) & fixed) == 0ull) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {                  // lane l owns bins 4l .. 4l+3; `incl` = candidates in its bins and all higher ones
+      const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+      const unsigned own = h0 + h1 + h2 + h3;
+      unsigned incl = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_down(incl, o, 64);
+        if (tid + o < 64) incl += t;
+      }
+      bool whole = false;            // the answer is known without looking at a bin: nothing, or every negative
+      if (shift == 56) {             // first pass: every negative was counted
+        const int n_negatives = (int)__shfl(incl, 0, 64), n_pos = P - n_negatives;
+        long long K = (long long)neg_per_pos * (long long)n_pos;
+        if (K < (long long)min_neg) K = min_neg;
+        if (K > (long long)n_negatives) K = n_negatives;
+        need = (int)K;
+        whole = need == 0 || need == n_negatives;
+        if (tid == 0) {
+          if (n_neg) n_neg[b] = need;
+          if (whole) { sh_cut = need == 0 ? ~0ull : 0ull; sh_need = 0; sh_done = 1; }   // no key is all ones: index < 2^31
+        }
+      }
+      const unsigned above = incl - own, k = (unsigned)need;
+      if (!whole && above < k && k <= incl) {                 // exactly one lane: the K-th lies in one of its four bins
+        unsigned a = above, cnt = h3;
+        int d = 3;
+        if (k > a + h3) { a += h3; cnt = h2; d = 2;
+          if (k > a + h2) { a += h2; cnt = h1; d = 1;
+            if (k > a + h1) { a += h1; cnt = h0; d = 0; } } }
+        sh_cut = cut | ((unsigned long long)(4 * tid + d) << shift);
+        sh_need = (int)(k - a);
+        sh_done = cnt == k - a;
+      }
+    }
+    __syncthreads();
+    cut = sh_cut;
+    need = sh_need;
+    if (sh_done) break;
+  }
+  return cut;
+}
+
+// --------------------------------------------------------- the three loss kernels
+// One body for mbx_loss_fwd_bwd, _mined and _focal (mbx.h).  One workgroup of kThreads per image: a strided pass over the
+// image's priors that writes both gradients and accumulates the two loss terms in double, a wave64 + LDS reduction, and
+// partial[2b], partial[2b + 1] for loss_final_kernel.
+//   FOCAL: a positive's -log c is weighted by w_pos * w^gamma, a counted negative's -log w by w_neg * c^gamma.  One powf per
+//     prior on top of the expf / logf (x^(gamma-1) is x^gamma / x); the term is formed in double from the float32 power and
+//     logarithm, the gradient in float32.  Without FOCAL the power and the weight are the constant 1 and gamma, w_pos and
+//     w_neg are not read.
+//   MINED: only the negatives at or over mined_select_cut's cut count, and the select writes n_neg[b].  Without MINED
+//     there is no select, no key and every negative counts; then n_neg[b] = P - positives is written under FOCAL (if n_neg
+//     is given) and nothing is counted without it: the plain entry has no n_neg.
+// gamma == 0 with unit weights is the plain function bit for bit: the power is then the constant 1 and the
+// gamma * x^(gamma-1) * log term is left out, so every product with the power or a weight is `x * 1.0f` (or 1.0 * x in
+// double), which is x; the file is built with -ffp-contract=off, so no product is fused into a sum either.  That is what
+// makes loss_kernel and loss_focal_kernel<false> at gamma = 0, weights (1, 1) agree (loss_mined_kernel and <true> likewise).
+// An unselected negative adds no loss and gets the gradient +0, not 0 * grad_scale: +0 whatever the sign of grad_scale.
+template <bool MINED, bool FOCAL>
+__device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                                          const float4* __restrict__ gt, const int* __restrict__ match, float alpha,
+                                          float grad_scale, int P, int G, float gamma, float w_pos, float w_neg,
+                                          int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
+                                          float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+  constexpr bool kCountPositives = FOCAL && !MINED;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  unsigned long long cut = 0ull;                             // no key is below 0: every negative counts
+  if (MINED) cut = mined_select_cut(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg, b, n_neg);
+  const bool modulated = FOCAL && gamma != 0.0f;
+
+  double loc_acc = 0.0, conf_acc = 0.0;
+  int n_pos = 0;
+  for (int p = tid; p < P; p += kThreads) {
+    const size_t i = (size_t)b * P + p;
+    const int m = match[i];
+    const float z = logits[i];
+    float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
+    float g;
+    if (MINED && m < 0 && mined_key(z, P, p) < cut) {
+      g = 0.f;                                              // an unselected negative: no loss, +0 whatever grad_scale is
+    } else {
+      const float s = is_logit ? 1.0f / (1.0f + expf(-z)) : z;
+      const float c = __fadd_rn(s, 1e-10f);                  // loss.py:74
+      const float w = __fadd_rn(__fsub_rn(1.0f, c), 1e-10f);
+      const float ds = is_logit ? s * (1.0f - s) : 1.0f;
+      const bool pos = m >= 0;
+      if (pos) {
+        const float4 l = decoded[i], q = gt[(size_t)b * G + m];
+        const float d0 = __fsub_rn(l.x, q.x), d1 = __fsub_rn(l.y, q.y), d2 = __fsub_rn(l.z, q.z), d3 = __fsub_rn(l.w, q.w);
+        loc_acc += (double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2 + (double)d3 * d3;   // loss.py:100
+        const float a = alpha * grad_scale;
+        dl = make_float4(a * d0, a * d1, a * d2, a * d3);
+        if (kCountPositives) ++n_pos;
+      }
+      // The two sides are one expression with c and w exchanged, -wt * base^gamma * log(arg): one logf and one powf for
+      // a wavefront that holds positives and negatives, not one of each per side.
+      const float arg = pos ? c : w, base = pos ? w : c, wt = FOCAL ? (pos ? w_pos : w_neg) : 1.0f;
+      const float lg = logf(arg);                                                         // loss.py:101
+      const float pw = modulated ? powf(base, gamma) : 1.0f;
+      conf_acc -= (double)wt * ((double)pw * (double)lg);
+      float d = (ds * pw) / arg;
+      if (modulated) d = d - gamma * (pw / base) * lg * ds;               // lg <= 0: both terms are >= 0, no cancellation
+      d = wt * d;
+      g = (pos ? -d : d) * grad_scale;
+    }
+    if (d_locs) d_locs[i] = dl;
+    if (d_logits) d_logits[i] = g;
+  }
+  loc_acc = wave_sum(loc_acc);
+  conf_acc = wave_sum(conf_acc);
+  __shared__ double red[kWaves][2];
+  __shared__ int pos_waves[kWaves];
+  if (kCountPositives) n_pos = wave_sum(n_pos);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = loc_acc; red[tid >> 6][1] = conf_acc;
+    if (kCountPositives) pos_waves[tid >> 6] = n_pos;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double a = 0.0, c = 0.0;
+    for (int w = 0; w < kWaves; ++w) { a += red[w][0]; c += red[w][1]; }
+    partial[2 * b] = a;
+    partial[2 * b + 1] = c;
+    if (kCountPositives && n_neg) {                          // every negative counts
+      int total = 0;
+      for (int w = 0; w < kWaves; ++w) total += pos_waves[w];
+      n_neg[b] = P - total;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kThreads)
+loss_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+            const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+            int P, int G, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
+            float* __restrict__ d_logits) {
+  loss_body<false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, 0.0f, 1.0f, 1.0f, 0, 0, partial,
+                          d_locs, d_logits, nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads)
+loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                  int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
+                  float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+  loss_body<true, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, 0.0f, 1.0f, 1.0f, neg_per_pos,
+                         min_neg, partial, d_locs, d_logits, n_neg);
+}
+
+template <bool MINED>
+__global__ void __launch_bounds__(kThreads)
+loss_focal_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                  const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                  int P, int G, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
+                  double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs, float* __restrict__ d_logits,
+                  int* __restrict__ n_neg) {
+  loss_body<MINED, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, gamma, w_pos, w_neg, neg_per_pos,
+                         min_neg, partial, d_locs, d_logits, n_neg);
+}
+
+}  // namespace
+
+// =============================================================================== C ABI
+extern "C" int mbx_decode_conf(const float* raw_locs, const float* logits, const float* priors, int B,
+                               int P, float eps_add, float* decoded, float* conf, mbx_stream_t stream) {
+  if (B < 0 || P <= 0) return MBX_ERR_INVALID_ARG;
+  if ((decoded && (!raw_locs || !priors)) || (conf && !logits)) return MBX_ERR_INVALID_ARG;
+  if (B == 0 || (!decoded && !conf)) return MBX_OK;
+  const int total = B * P;
+  int blocks = (total + kThreads - 1) / kThreads;
+  if (blocks > 2048) blocks = 2048;
+  MBX_ENTER();
+  hipLaunchKernelGGL(decode_conf_kernel, dim3(blocks), dim3(kThreads), 0, mbx_s(stream),
+                     reinterpret_cast<const float4*>(raw_locs), logits, reinterpret_cast<const float4*>(priors),
+                     total, P, eps_add, reinterpret_cast<float4*>(decoded), conf);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+static size_t match_lds_bytes(int P, int G) { return (size_t)P * 36 + (size_t)G * 16 + 16; }
+
+extern "C" size_t mbx_match_workspace_bytes(int, int, int) { return 0; }
+
+extern "C" int mbx_match(const float* decoded, const float* conf, const float* gt, const int32_t* n_gt,
+                         float alpha, int B, int P, int G, int32_t* match, int32_t* status, void*, size_t,
+                         mbx_stream_t stream) {
+  if (!decoded || !conf || !gt || !n_gt || !match || !status || B < 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (B == 0) return MBX_OK;
+  const size_t lds = match_lds_bytes(P, G);
+  if (lds > 150 * 1024) return MBX_ERR_UNSUPPORTED;        // P > ~4200 at G=100
+  static const int force_nt = mbx_env_int("MBX_MATCH_THREADS", 0);     // (tools/match_bench.py)
+  const int nthreads = force_nt ? force_nt : (P > 1536 ? 512 : kThreads);
+  MBX_ENTER();
+  if (lds > 64 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess) return MBX_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(match_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
+                     reinterpret_cast<const float4*>(decoded), conf, reinterpret_cast<const float4*>(gt), n_gt,
+                     alpha, P, G, match, status);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" int mbx_match_extend(const float* priors, const float* gt, const int32_t* n_gt, const int32_t* status,
+                                float iou_threshold, int B, int P, int G, int32_t* match, int32_t* n_extra,
+                                mbx_stream_t stream) {
+  if (!priors || !gt || !n_gt || !status || !match || B < 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (!(iou_threshold > 0.0f && iou_threshold <= 1.0f)) return MBX_ERR_INVALID_ARG;      // a NaN fails both
+  const size_t lds = (size_t)G * sizeof(StagedBox);
+  if (lds > 60 * 1024) return MBX_ERR_UNSUPPORTED;           // G > 1536: under the 64 KB a launch gets without asking
+  if (B == 0) return MBX_OK;
+  const int nthreads = P >= 1024 ? 1024 : (P + 63) / 64 * 64;
+  MBX_ENTER();
+  hipLaunchKernelGGL(match_extend_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
+                     reinterpret_cast<const float4*>(priors), reinterpret_cast<const float4*>(gt), n_gt, status,
+                     (double)iou_threshold, P, G, match, n_extra);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" size_t mbx_loss_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 1) * 2 * sizeof(double); }
+extern "C" size_t mbx_loss_mined_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+extern "C" size_t mbx_loss_focal_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+
+// What the three loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
+// the kernel of `kind`, then loss_final_kernel.  An entry checks its own arguments first; those and the ones here all
+// answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal mines iff neg_per_pos != 0.
+enum class LossKind { kPlain, kMined, kFocal };
+
+static int launch_loss(LossKind kind, const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                       const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                       float* d_raw_locs, float* d_logits, float gamma, float w_pos, float w_neg, int neg_per_pos,
+                       int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes, mbx_stream_t stream) {
+  if (!decoded || !logits || !gt || !match || !loss2 || B <= 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < mbx_loss_workspace_bytes(B)) return MBX_ERR_WORKSPACE;
+  double* partial = reinterpret_cast<double*>(workspace);
+  const float4* dec4 = reinterpret_cast<const float4*>(decoded);
+  const float4* gt4 = reinterpret_cast<const float4*>(gt);
+  float4* dl4 = reinterpret_cast<float4*>(d_raw_locs);
+  MBX_ENTER();
+  switch (kind) {
+    case LossKind::kPlain:
+      hipLaunchKernelGGL(loss_kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream), dec4, logits, conf_is_logit, gt4, match,
+                         alpha, grad_scale, P, G, partial, dl4, d_logits);
+      break;
+    case LossKind::kMined:
+      hipLaunchKernelGGL(loss_mined_kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream), dec4, logits, conf_is_logit, gt4,
+                         match, alpha, grad_scale, P, G, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg);
+      break;
+    case LossKind::kFocal:
+      hipLaunchKernelGGL(neg_per_pos ? loss_focal_kernel<true> : loss_focal_kernel<false>, dim3(B), dim3(kThreads), 0,
+                         mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, gamma, w_pos,
+                         w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg);
+      break;
+  }
+  MBX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+extern "C" int mbx_loss_fwd_bwd(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                float* d_raw_locs, float* d_logits, void* workspace, size_t workspace_bytes,
+                                mbx_stream_t stream) {
+  return launch_loss(LossKind::kPlain, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, 0.0f, 1.0f, 1.0f, 0, 0, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mbx_loss_fwd_bwd_mined(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                      const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                      float* d_raw_locs, float* d_logits, int neg_per_pos, int min_neg, int32_t* n_neg,
+                                      void* workspace, size_t workspace_bytes, mbx_stream_t stream) {
+  if (neg_per_pos < 1 || min_neg < 0) return MBX_ERR_INVALID_ARG;
+  return launch_loss(LossKind::kMined, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, 0.0f, 1.0f, 1.0f, neg_per_pos, min_neg, n_neg, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mbx_loss_fwd_bwd_focal(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                      const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                      float* d_raw_locs, float* d_logits, float gamma, float w_pos, float w_neg,
+                                      int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes,
+                                      mbx_stream_t stream) {
+  if (!(gamma >= 0.0f && gamma <= 10.0f)) return MBX_ERR_INVALID_ARG;                      // a NaN fails both
+  if (!(w_pos >= 0.0f && w_neg >= 0.0f) || isinf(w_pos) || isinf(w_neg)) return MBX_ERR_INVALID_ARG;
+  if (neg_per_pos < 0 || min_neg < 0 || (neg_per_pos == 0 && min_neg > 0)) return MBX_ERR_INVALID_ARG;
+  return launch_loss(LossKind::kFocal, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace, workspace_bytes, stream);
+}

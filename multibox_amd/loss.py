@@ -125,12 +125,21 @@ class MultiboxLoss:
         self.d_locs = torch.empty((self.B, self.P, 4), **f)
         self.d_logits = torch.empty((self.B, self.P), **f)
         self.neg_per_pos, self.min_neg, self.n_neg = neg_per_pos, min_neg, None
-        ws_bytes = _lib.lib().mbx_loss_workspace_bytes(self.B)
+        mining = (0, 0, None)                                  # (neg_per_pos, min_neg, n_neg) as the entries take them
         if neg_per_pos is not None:
             self.n_neg = torch.zeros((self.B,), dtype=torch.int32, device=device)
-            ws_bytes = _lib.lib().mbx_loss_mined_workspace_bytes(self.B, self.P)
+            mining = (neg_per_pos, min_neg, self.n_neg.data_ptr())
+        # the entry forward_backward calls, the arguments it has between the common ones and the workspace, its workspace
+        l = _lib.lib()
         if self.focal is not None:
-            ws_bytes = _lib.lib().mbx_loss_focal_workspace_bytes(self.B, self.P)
+            self.entry, self.entry_args = "mbx_loss_fwd_bwd_focal", self.focal + mining
+            ws_bytes = l.mbx_loss_focal_workspace_bytes(self.B, self.P)
+        elif neg_per_pos is not None:
+            self.entry, self.entry_args = "mbx_loss_fwd_bwd_mined", mining
+            ws_bytes = l.mbx_loss_mined_workspace_bytes(self.B, self.P)
+        else:
+            self.entry, self.entry_args = "mbx_loss_fwd_bwd", ()
+            ws_bytes = l.mbx_loss_workspace_bytes(self.B)
         self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
         self.match_iou_threshold, self.n_extra = match_iou_threshold, None
         if match_iou_threshold is not None:
@@ -159,28 +168,10 @@ class MultiboxLoss:
             _lib.check(l.mbx_match_extend(self.priors.data_ptr(), gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),
                                           self.status.data_ptr(), self.match_iou_threshold, B, P, G,
                                           self.match.data_ptr(), self.n_extra.data_ptr(), s), "mbx_match_extend")
-        if self.focal is not None:
-            gamma, w_pos, w_neg = self.focal
-            mined = self.neg_per_pos is not None
-            _lib.check(l.mbx_loss_fwd_bwd_focal(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
-                                                gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
-                                                B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
-                                                self.d_logits.data_ptr(), gamma, w_pos, w_neg,
-                                                self.neg_per_pos if mined else 0, self.min_neg if mined else 0,
-                                                self.n_neg.data_ptr() if mined else None, self.ws.data_ptr(),
-                                                self.ws.numel(), s), "mbx_loss_fwd_bwd_focal")
-        elif self.neg_per_pos is None:
-            _lib.check(l.mbx_loss_fwd_bwd(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
-                                          gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
-                                          B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(), self.d_logits.data_ptr(),
-                                          self.ws.data_ptr(), self.ws.numel(), s), "mbx_loss_fwd_bwd")
-        else:
-            _lib.check(l.mbx_loss_fwd_bwd_mined(self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)),
-                                                gt_bboxes.data_ptr(), self.match.data_ptr(), self.alpha, float(grad_scale),
-                                                B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
-                                                self.d_logits.data_ptr(), self.neg_per_pos, self.min_neg,
-                                                self.n_neg.data_ptr(), self.ws.data_ptr(), self.ws.numel(), s),
-                       "mbx_loss_fwd_bwd_mined")
+        common = (self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)), gt_bboxes.data_ptr(),
+                  self.match.data_ptr(), self.alpha, float(grad_scale), B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
+                  self.d_logits.data_ptr())
+        _lib.check(getattr(l, self.entry)(*common, *self.entry_args, self.ws.data_ptr(), self.ws.numel(), s), self.entry)
         return self.loss2, self.d_locs, self.d_logits
 
 

@@ -137,7 +137,7 @@ def tie_free_image(P, n, alpha, seed):
 
 
 def match_lds_bytes(P, G):
-    """The host's formula (postproc.hip, match_lds_bytes): 36 bytes a prediction, 16 a gt, 16 of padding."""
+    """The host's formula (loss.hip, match_lds_bytes): 36 bytes a prediction, 16 a gt, 16 of padding."""
     return 36 * P + 16 * G + 16
 
 

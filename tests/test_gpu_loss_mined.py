@@ -8,68 +8,16 @@ import numpy as np
 import pytest
 
 from tests import mined_oracle as MO
+from tests import loss_cases as LC
+from tests.loss_cases import ALPHA, SENTINEL, SHAPES, _forward_backward, batch, cut_splits_a_run, gpu, make_case  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ALPHA = 1000.0
-SHAPES = [(3, 13, 13), (4, 70, 5), (4, 646, 13), (2, 3199, 100)]
-SENTINEL = 7.0
 
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from multibox_amd import _lib
-    return torch, _lib.lib()
-
-
-def make_case(B, P, G, kind="plain", seed=0):
-    """Seeded inputs with a hand-made match: image 0 has no positive, image 1 the most there can be (min(G, P): at
-    (3, 13, 13) it has no negative at all), the others a random number.  `x` holds confidences in (0, 1) -- `kind` says
-    which -- and `z` logits."""
-    rng = np.random.RandomState(1000 * P + B + seed)
-    n_pos = rng.randint(1, min(G, P) + 1, B)
-    n_pos[0], n_pos[1] = 0, min(G, P)
-    match = -np.ones((B, P), np.int32)
-    for b in range(B):
-        match[b, rng.permutation(P)[:n_pos[b]]] = rng.permutation(G)[:n_pos[b]]
-    x = rng.uniform(0.01, 0.99, (B, P)).astype(np.float32)
-    if kind == "quantised":                                   # 16 levels: long runs of equal keys
-        x = (np.floor(x * 16) / 16).astype(np.float32)
-    elif kind == "zeros":                                     # most entries +0.0 or -0.0: one run of equal keys, two bit patterns
-        r = rng.uniform(size=(B, P))
-        x = np.where(r < 0.4, np.float32(0.0), np.where(r < 0.8, np.float32(-0.0), x)).astype(np.float32)
-    return dict(B=B, P=P, G=G, n_pos=n_pos, match=match, x=x, z=(rng.randn(B, P) * 2 - 1).astype(np.float32),
-                dec=rng.uniform(0, 1, (B, P, 4)).astype(np.float32), gt=rng.uniform(0, 1, (B, G, 4)).astype(np.float32))
-
-
-def call(gpu, c, conf_in, is_logit, neg_per_pos=3, min_neg=0, rows=None, grad_scale=1.0, mined=True, ws_short=0,
-         prefill=None):
-    """One call of the C ABI on images `rows` of case c -> (status, dict of numpy outputs)."""
-    torch, l = gpu
-    rows = slice(None) if rows is None else rows
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a[rows])).cuda()
-    dec, x, gt, match = dev(c["dec"]), dev(conf_in), dev(c["gt"]), dev(c["match"])
-    B, P, G = match.shape[0], c["P"], c["G"]
-    fill = (lambda *s, dt=torch.float32: torch.full(s, prefill, dtype=dt, device="cuda")) if prefill is not None else \
-        (lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device="cuda"))
-    loss2, dl, dz, n_neg = fill(2), fill(B, P, 4), fill(B, P), fill(B, dt=torch.int32)
-    s = torch.cuda.current_stream().cuda_stream
-    if mined:
-        ws = torch.empty((l.mbx_loss_mined_workspace_bytes(B, P),), dtype=torch.uint8, device="cuda")
-        st = l.mbx_loss_fwd_bwd_mined(dec.data_ptr(), x.data_ptr(), int(is_logit), gt.data_ptr(), match.data_ptr(), ALPHA,
-                                      grad_scale, B, P, G, loss2.data_ptr(), dl.data_ptr(), dz.data_ptr(), neg_per_pos,
-                                      min_neg, n_neg.data_ptr(), ws.data_ptr(), ws.numel() - ws_short, s)
-    else:
-        ws = torch.empty((l.mbx_loss_workspace_bytes(B),), dtype=torch.uint8, device="cuda")
-        st = l.mbx_loss_fwd_bwd(dec.data_ptr(), x.data_ptr(), int(is_logit), gt.data_ptr(), match.data_ptr(), ALPHA,
-                                grad_scale, B, P, G, loss2.data_ptr(), dl.data_ptr(), dz.data_ptr(), ws.data_ptr(),
-                                ws.numel(), s)
-    torch.cuda.synchronize()
-    return st, dict(loss2=loss2.cpu().numpy(), dl=dl.cpu().numpy(), dz=dz.cpu().numpy(), n_neg=n_neg.cpu().numpy())
+def call(gpu, c, conf_in, is_logit, neg_per_pos=3, min_neg=0, mined=True, **kw):
+    """loss_cases.call on the mined entry, neg_per_pos = 3 unless said; mined=False: on the plain entry."""
+    return LC.call(gpu, c, conf_in, is_logit, entry="mined" if mined else "plain", neg_per_pos=neg_per_pos, min_neg=min_neg,
+                   **kw)
 
 
 def check_selection(c, out, mask, K):
@@ -79,17 +27,6 @@ def check_selection(c, out, mask, K):
     assert np.array_equal((out["dz"] != 0) & neg, mask)
     assert np.all(out["dz"].view(np.uint32)[neg & ~mask] == 0)            # +0.0f by bits
     assert np.all(out["dz"][~neg] < 0)                                    # positives: -1/c
-
-
-def cut_splits_a_run(c, mask):
-    """Images in which negatives with bit-equal keys lie on both sides of the cut."""
-    key = MO.score_order_key(c["x"])
-    hit = []
-    for b in range(c["B"]):
-        neg = c["match"][b] < 0
-        if np.intersect1d(key[b][neg & mask[b]], key[b][neg & ~mask[b]]).size:
-            hit.append(b)
-    return hit
 
 
 # ------------------------------------------------------------------------------------------------- selection is exact
@@ -157,6 +94,47 @@ def test_all_negatives_kept_is_the_unmined_function_byte_for_byte(gpu, B, P, G, 
         assert mined[k].tobytes() == plain[k].tobytes(), k
 
 
+# ---------------------------------------------------------------------- the gradients, against float32 numpy: exact
+def exact_gradients(c, grad_scale, mask=None):
+    """d_logits and d_raw_locs for confidences `x` given as they are (conf_is_logit = 0: no expf), restated in numpy
+    float32.  Every step of the kernel is then one correctly rounded float32 operation -- c = x + 1e-10f,
+    w = (1 - c) + 1e-10f, (-1 / c) * grad_scale on a positive, (1 / w) * grad_scale on a counted negative,
+    (alpha * grad_scale) * (l - g) -- and numpy float32 does the same operations.  mask: the negatives that count (None =
+    all); the others get +0."""
+    f = np.float32
+    pos = c["match"] >= 0
+    cc = c["x"] + f(1e-10)
+    w = (f(1) - cc) + f(1e-10)
+    dz = np.where(pos, (f(-1) / cc) * f(grad_scale), (f(1) / w) * f(grad_scale)).astype(f)
+    if mask is not None:
+        dz[~pos & ~mask] = f(0)
+    dl = np.zeros(c["dec"].shape, f)
+    a = f(ALPHA) * f(grad_scale)
+    for b in range(c["B"]):
+        p = np.nonzero(pos[b])[0]
+        dl[b, p] = a * (c["dec"][b, p] - c["gt"][b, c["match"][b, p]])
+    assert dz.dtype == f and dl.dtype == f
+    return dz, dl
+
+
+@pytest.mark.parametrize("B,P,G", SHAPES[:3])                 # under one wavefront with an image without negatives; a
+@pytest.mark.parametrize("kind", ["plain", "zeros"])          # partial second wavefront; three strides, the last ragged
+@pytest.mark.parametrize("grad_scale", [1.0, 0.5])
+@pytest.mark.parametrize("entry", ["plain", "mined", "focal"])
+def test_confidence_input_gradients_are_exact(gpu, B, P, G, kind, grad_scale, entry):
+    c = make_case(B, P, G, kind)
+    mask = MO.select(c["x"], c["match"], 3, 0)[0] if entry == "mined" else None
+    kw = dict(plain={}, mined=dict(neg_per_pos=3), focal=dict(gamma=0.0, alpha=None))[entry]
+    st, out = LC.call(gpu, c, c["x"], 0, entry=entry, grad_scale=grad_scale, **kw)
+    assert st == 0
+    dz, dl = exact_gradients(c, grad_scale, mask)
+    print("d_logits: %d of %d differ; d_raw_locs: %d of %d differ" % (
+        (out["dz"].view(np.uint32) != dz.view(np.uint32)).sum(), dz.size,
+        (out["dl"].view(np.uint32) != dl.view(np.uint32)).sum(), dl.size))
+    assert out["dz"].tobytes() == dz.tobytes()
+    assert out["dl"].tobytes() == dl.tobytes()
+
+
 # ------------------------------------------------------------------------------------------------------- independence
 @pytest.mark.parametrize("B,P,G", SHAPES)
 def test_an_image_depends_on_its_own_row_only_and_calls_repeat(gpu, B, P, G):
@@ -204,31 +182,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(gpu, kw, status):
 
 
 # ------------------------------------------------------------------------------------------------ through MultiboxLoss
-@pytest.fixture(scope="module")
-def batch():
-    """Raw network outputs and ground truth for MultiboxLoss at P = 646, B = 4 (image 1 without boxes)."""
-    from multibox_amd import priors as PR
-    priors = np.array(PR.generate_priors([1, 2, 3, 1 / 2., 1 / 3.]), np.float32)
-    rng = np.random.RandomState(5)
-    B, P, G = 4, priors.shape[0], 13
-    raw = (rng.randn(B, P, 4) * 0.05).astype(np.float32)
-    logits = (rng.randn(B, P) * 2 - 2).astype(np.float32)
-    n = np.array([G, 0, 3, 7], np.int32)
-    gt = np.zeros((B, G, 4), np.float32)
-    for b in range(B):
-        xy = rng.uniform(0, .7, (n[b], 2)); wh = rng.uniform(.05, .3, (n[b], 2))
-        gt[b, :n[b], :2] = xy; gt[b, :n[b], 2:] = xy + wh
-    return dict(priors=priors, raw=raw, logits=logits, gt=gt, n=n, B=B, P=P, G=G)
-
-
-def _forward_backward(torch, ml, batch):
-    out = ml.forward_backward(torch.from_numpy(batch["raw"]).cuda(), torch.from_numpy(batch["logits"]).cuda(),
-                              torch.from_numpy(batch["gt"]).cuda(), torch.from_numpy(batch["n"]).cuda())
-    torch.cuda.synchronize()
-    assert int(ml.status.max()) == 0
-    return [t.cpu().numpy() for t in out]
-
-
 def test_multibox_loss_without_the_switch_is_unchanged(gpu, batch):
     torch, _ = gpu
     from multibox_amd import loss as L

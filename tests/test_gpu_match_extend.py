@@ -11,23 +11,14 @@ import numpy as np
 import pytest
 
 from tests import extend_oracle as EO
+from tests import loss_cases as LC
 from tests import mined_oracle as MO
+from tests.loss_cases import ALPHA, batch, gpu  # noqa: F401  (the fixtures are found by name)
 
 pytestmark = pytest.mark.gpu
 
-ALPHA = 1000.0
 SHAPES = [(3, 13, 13), (4, 70, 5), (4, 646, 13), (2, 3199, 100)]
 SENTINEL = -77
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    from multibox_amd import _lib
-    return torch, _lib.lib()
 
 
 @functools.lru_cache(maxsize=None)
@@ -220,29 +211,9 @@ def test_more_boxes_than_the_lds_holds_is_unsupported(gpu):
 
 
 # ------------------------------------------------------------------------------------------------ through MultiboxLoss
-@pytest.fixture(scope="module")
-def batch():
-    """Raw network outputs and ground truth for MultiboxLoss at P = 646, B = 4 (image 1 without boxes)."""
-    from multibox_amd import priors as PR
-    priors = np.array(PR.generate_priors([1, 2, 3, 1 / 2., 1 / 3.]), np.float32)
-    rng = np.random.RandomState(5)
-    B, P, G = 4, priors.shape[0], 13
-    raw = (rng.randn(B, P, 4) * 0.05).astype(np.float32)
-    logits = (rng.randn(B, P) * 2 - 2).astype(np.float32)
-    n = np.array([G, 0, 3, 7], np.int32)
-    gt = np.zeros((B, G, 4), np.float32)
-    for b in range(B):
-        xy = rng.uniform(0, .7, (n[b], 2)); wh = rng.uniform(.05, .3, (n[b], 2))
-        gt[b, :n[b], :2] = xy; gt[b, :n[b], 2:] = xy + wh
-    return dict(priors=priors, raw=raw, logits=logits, gt=gt, n=n, B=B, P=P, G=G)
-
-
 def _forward_backward(torch, ml, batch):
-    out = ml.forward_backward(torch.from_numpy(batch["raw"]).cuda(), torch.from_numpy(batch["logits"]).cuda(),
-                              torch.from_numpy(batch["gt"]).cuda(), torch.from_numpy(batch["n"]).cuda())
-    torch.cuda.synchronize()
-    assert int(ml.status.max()) == 0
-    return [t.cpu().numpy() for t in out] + [ml.match.cpu().numpy()]
+    """loss_cases' three outputs and the match they were computed on."""
+    return LC._forward_backward(torch, ml, batch) + [ml.match.cpu().numpy()]
 
 
 @pytest.fixture(scope="module")

@@ -3,6 +3,7 @@
 // launch family -- conv5.hip (persistent igemm5), conv7.hip (panel-resident pointwise igemm7), convd.hip (direct 3x3 /
 // whole-width / stem), convr.hip (resident-image and pixel-resident pointwise).  gfx950 only.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "grid_barrier.h"
 
@@ -125,6 +126,31 @@ constexpr int kThreads = 256;
 // CUs the persistent launches size their grids by (and the grouped weight gradient plans for); no device visible -- planning
 // or mbx_conv_supported on a CPU-only host: MI355X
 inline int conv_cus() { const int n = mbx_cu_count(); return n ? n : 256; }
+
+// what the direct and the resident families accept of a descriptor's epilogue: a bf16 store (with or without statistics) or
+// the affine one without statistics; nothing accumulated, masked, scaled or summed for a batch-norm backward
+inline bool store_or_affine_only(const ConvK& k) {
+  return (k.epi == MBX_EPI_STORE || k.epi == MBX_EPI_AFFINE) && !k.accumulate && !k.skip && !k.bits && k.rscale == 0.f && !k.bw_n &&
+         !(k.epi == MBX_EPI_AFFINE && k.stats);
+}
+
+// The launch of those families: kern(EV as a std::integral_constant) names the kernel of epilogue EV = 0 (store), 1 (store +
+// statistics) or 3 (affine), all of one signature (ConvK, Q); its dynamic-LDS attribute is set at its first launch.  (`attr`
+// is one array per instantiation of this template, i.e. per kern: every launcher passes a lambda of its own.)
+template <typename Q, typename F>
+inline int launch_by_ev(const ConvK& k, const Q& q, int grid, int threads, int lds, hipStream_t s, F kern) {
+  static bool attr[3] = {false, false, false};
+  const int ev = k.epi == MBX_EPI_AFFINE ? 2 : k.stats ? 1 : 0;
+  void (*const fn)(const ConvK, const Q) = ev == 2 ? kern(std::integral_constant<int, 3>())
+                                           : ev   ? kern(std::integral_constant<int, 1>()) : kern(std::integral_constant<int, 0>());
+  if (!attr[ev]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr[ev] = true;
+  }
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, s, k, q);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
 
 // magic number + shift of the kernels' division by d (fast_div)
 inline void set_magic(unsigned d, unsigned& mg, unsigned& sh) {

@@ -15,7 +15,7 @@
 // the igemm kernels', so the results are bit-identical to them (tests/test_gpu_conv.py::test_conv_direct3).
 // Epilogues: bf16 store (EV = 0), store + batch-norm statistics (EV = 1: ONE partial row per workgroup, summed over its
 // tiles in a fixed order: mbx_conv_stats_rows = the grid size).
-#include "conv_common.h"
+#include "direct_epilogue.h"
 
 namespace {
 
@@ -30,28 +30,31 @@ struct DirK { int N, H_out, tiles_h, tiles_w, ntiles; };
 template <int CI>
 __device__ __forceinline__ int dkey(int pix) { return CI == 32 ? ((pix >> 2) & 3) : ((pix >> 1) & 7); }
 
-// Filter rows are fed to the MFMA in a PERMUTED order (as in conv_igemm3_kernel): LDS row 16 a + f of a tap holds output
-// channel dperm(a, f), so that blocks 2A and 2A + 1 leave a lane EIGHT consecutive channels of one pixel = one 16-byte store
-// (four lanes cover 64 contiguous bytes; with the plain order a 128-byte pixel row went out as four 32-byte pieces and the
-// 32 -> 64 layer ran at 2.4x its HBM time).  A trailing unpaired block (C_out 48: channels 32..47) keeps the plain order.
-template <int CO>
-__device__ __forceinline__ int dperm(int a, int f) {
-  return (a < (CO / 32) * 2) ? 32 * (a >> 1) + 8 * (f >> 2) + 4 * (a & 1) + (f & 3) : 16 * a + f;
-}
+constexpr int direct_stores(int CO) { return 2 * (CO / 32 + (CO % 32 ? 1 : 0)); }   // store instructions of a tile's epilogue, per wave
+
+// what kernel and launcher of conv_direct3_kernel<CI, CO, .> both read
+template <int CI, int CO>
+struct D3G {
+  static constexpr int C8 = CI / 8, KC = CI / 32, NA = CO / 16;
+  static constexpr int PCH = kDPH * kDPW * C8;            // 16-byte chunks of a patch
+  static constexpr int PROUNDS = (PCH + kDThreads - 1) / kDThreads;
+  static constexpr int PBUF = PROUNDS * kDThreads;        // chunks per patch buffer (the tail is zero fill)
+  static constexpr int WCH = 9 * CO * C8;                 // chunks of the filter image [tap][co][c8]
+  static constexpr int WROUNDS = (WCH + kDThreads - 1) / kDThreads;
+  static constexpr int NBUF = CI == 32 ? 3 : 2;           // patch buffers: three where 160 KB hold them
+  static constexpr int NS = direct_stores(CO);
+  static constexpr int LDS_BYTES = (WROUNDS * kDThreads + NBUF * PBUF) * 16 + 8 * CO * 2 * 4;   // filter image, ring, red
+};
 
 template <int CI, int CO, int EV>
 __global__ void __launch_bounds__(kDThreads)
 conv_direct3_kernel(const ConvK p, const DirK q) {
-  constexpr int C8 = CI / 8, KC = CI / 32, NA = CO / 16;
-  constexpr int PCH = kDPH * kDPW * C8;                   // 16-byte chunks of a patch
-  constexpr int PROUNDS = (PCH + kDThreads - 1) / kDThreads;
-  constexpr int PBUF = PROUNDS * kDThreads;               // chunks per patch buffer (the tail is zero fill)
-  constexpr int WCH = 9 * CO * C8;                        // chunks of the filter image [tap][co][c8]
-  constexpr int WROUNDS = (WCH + kDThreads - 1) / kDThreads;
+  using Geo = D3G<CI, CO>;
+  constexpr int C8 = Geo::C8, KC = Geo::KC, NA = Geo::NA, PCH = Geo::PCH, PROUNDS = Geo::PROUNDS, PBUF = Geo::PBUF;
+  constexpr int WCH = Geo::WCH, WROUNDS = Geo::WROUNDS;
   // patch ring: NBUF buffers, the loads run D = NBUF - 1 tiles ahead (three buffers where 160 KB hold them: C_in 32).  One
   // workgroup per CU has nothing else to cover the ~2 us of a patch's HBM latency with: at D = 1 every tile waited for it.
-  constexpr int NBUF = CI == 32 ? 3 : 2, D = NBUF - 1;
-  constexpr int NS = 2 * (CO / 32 + (CO % 32 ? 1 : 0));   // store instructions of a tile's epilogue, per wave
+  constexpr int NBUF = Geo::NBUF, D = NBUF - 1, NS = Geo::NS;
   extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
   u32x4* const wimg = smem;                               // [9][CO][C8] (swizzled)
   u32x4* const pbuf = smem + WROUNDS * kDThreads;         // the patch ring
@@ -110,26 +113,8 @@ conv_direct3_kernel(const ConvK p, const DirK q) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) { s1[a][r] = 0.f; s2[a][r] = 0.f; }
   const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y, p.y_bytes);
-  // EV = 3 (folded batch norm of the inference / --fine_tune forward, detect.py:313-326): y = act(acc * scale[c] + shift[c]),
-  // the expression of the implicit-GEMM kernels' affine epilogue; the lane's channels are the same for every tile
-  constexpr int NPq = CO / 32;
-  float sc8[NPq > 0 ? NPq : 1][8], sh8[NPq > 0 ? NPq : 1][8], sc4[4], sh4[4];
-  if constexpr (EV == 3) {
-#pragma unroll
-    for (int A = 0; A < NPq; ++A)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = 32 * A + 8 * fch + j;
-        sc8[A][j] = (p.scale && c < p.C_out) ? p.scale[c] : 1.f;
-        sh8[A][j] = (p.shiftv && c < p.C_out) ? p.shiftv[c] : 0.f;
-      }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = 2 * NPq * 16 + 4 * fch + j;
-      sc4[j] = (p.scale && c < p.C_out) ? p.scale[c] : 1.f;
-      sh4[j] = (p.shiftv && c < p.C_out) ? p.shiftv[c] : 0.f;
-    }
-  }
+  DirAffine<NA> af;                                       // (the lane's channels are the same for every tile)
+  direct_affine_load<EV, NA>(p, 0, p.C_out, fch, af);
 
   // The filter fragments are the same for every tile: where they fit the register file (a 512-thread workgroup alone on its
   // CU may use 256 registers per lane) they are read from LDS ONCE -- per tile that leaves the two pixel fragments of a tap,
@@ -189,74 +174,15 @@ conv_direct3_kernel(const ConvK p, const DirK q) {
               acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[a], pf[b], acc[a][b], 0, 0, 0);
         }
       }
-    // ---- epilogue: blocks 2A, 2A + 1 -> 8 consecutive channels (32 A + 8 fch ..) of pixel (wave, 16 b + frow): 16-byte stores;
-    // an unpaired last block: 4 consecutive channels, 8-byte stores
-    {
+    {  // ---- epilogue: pixel (wave, 16 b + frow) of the tile
       const int tw = t % q.tiles_w, r_ = t / q.tiles_w, th = r_ % q.tiles_h, img = r_ / q.tiles_h;
       const int oh = th * kDTH + wave;
-      constexpr int NP = CO / 32;                           // paired blocks
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int ow = tw * kDTW + b * 16 + frow;
         const bool pv = oh < q.H_out && ow < p.W_out;
         const int pix_off = img * p.y_img_stride + (oh * p.W_out + ow) * p.ldy;
-#pragma unroll
-        for (int A = 0; A < NP; ++A) {
-          const int c0 = 32 * A + 8 * fch;
-          const bool ok = pv && c0 < p.C_out;               // C_out % 8 == 0: a group of eight is all in or all out
-          unsigned h8[8];
-          float v8[8];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { v8[r] = acc[2 * A][b][r]; v8[4 + r] = acc[2 * A + 1][b][r]; }
-          if constexpr (EV == 3) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v8[j] = v8[j] * sc8[A][j] + sh8[A][j];
-            if (p.relu) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) v8[j] = relu_f(v8[j]);
-            }
-          }
-          unsigned h2[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) h2[j] = pack2bf(v8[2 * j], v8[2 * j + 1]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) h8[j] = (j & 1) ? (h2[j >> 1] >> 16) : (h2[j >> 1] & 0xffffu);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{h2[0], h2[1], h2[2], h2[3]},
-                                                 yr, ok ? (int)((pix_off + c0) * 2) : (int)kOOB, 0, 0);
-          if constexpr (EV == 1) {
-            if (ok) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float f0 = bf2f((unsigned short)h8[r]), f1 = bf2f((unsigned short)h8[4 + r]);
-                s1[2 * A][r] += f0; s2[2 * A][r] += f0 * f0;
-                s1[2 * A + 1][r] += f1; s2[2 * A + 1][r] += f1 * f1;
-              }
-            }
-          }
-        }
-        if constexpr (NA > 2 * NP) {                        // C_out 48: channels 32 .. 47 in the plain order
-          constexpr int a = 2 * NP;
-          const int c0 = a * 16 + 4 * fch;
-          const bool ok = pv && c0 < p.C_out;
-          unsigned h4[4];
-          float v4[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float v = acc[a][b][r];
-            if constexpr (EV == 3) { v = v * sc4[r] + sh4[r]; if (p.relu) v = relu_f(v); }
-            v4[r] = v;
-          }
-          const unsigned g2[2] = {pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3])};
-          h4[0] = g2[0] & 0xffffu; h4[1] = g2[0] >> 16; h4[2] = g2[1] & 0xffffu; h4[3] = g2[1] >> 16;
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2{g2[0], g2[1]}, yr,
-                                                ok ? (int)((pix_off + c0) * 2) : (int)kOOB, 0, 0);
-          if constexpr (EV == 1) {
-            if (ok) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) { const float f = bf2f((unsigned short)h4[r]); s1[a][r] += f; s2[a][r] += f * f; }
-            }
-          }
-        }
+        direct_store_pixel<EV>(p, yr, acc, b, pv, pix_off, 0, p.C_out, fch, af, s1, s2);
       }
     }
     if (more) {
@@ -309,17 +235,23 @@ conv_direct3_kernel(const ConvK p, const DirK q) {
 constexpr int kSPH = 2 * kDTH + 1, kSPW = 2 * kDTW + 1;   // input patch of an output tile (stride 2, 3 x 3)
 constexpr int kSWRow = 13;                                // filter image row: 12 chunks of K (9 taps + 3 of zeros) padded to 13 (conflict-free reads)
 
+struct StemG {
+  static constexpr int CO = 32, NA = 2;
+  static constexpr int PCH = kSPH * kSPW;                 // 16-byte chunks of a patch (one per pixel)
+  static constexpr int PROUNDS = (PCH + kDThreads - 1) / kDThreads;
+  static constexpr int PBUF = PROUNDS * kDThreads;
+  static constexpr int WCH = CO * kSWRow;                 // the filter image: one round
+  static constexpr int NBUF = 3;
+  static constexpr int NS = 2;                            // store instructions of a tile's epilogue, per wave
+  static constexpr int LDS_BYTES = (kDThreads + NBUF * PBUF) * 16 + 8 * CO * 2 * 4;   // filter image, ring, red
+};
+
 template <int EV>
 __global__ void __launch_bounds__(kDThreads)
 conv_stem_kernel(const ConvK p, const DirK q) {
-  constexpr int CO = 32, NA = 2;
-  constexpr int PCH = kSPH * kSPW;                        // 16-byte chunks of a patch (one per pixel)
-  constexpr int PROUNDS = (PCH + kDThreads - 1) / kDThreads;
-  constexpr int PBUF = PROUNDS * kDThreads;
-  constexpr int WCH = CO * kSWRow;
+  constexpr int CO = StemG::CO, NA = StemG::NA, PCH = StemG::PCH, PROUNDS = StemG::PROUNDS, PBUF = StemG::PBUF, WCH = StemG::WCH;
   static_assert(WCH <= kDThreads, "filter image in one round");
-  constexpr int NBUF = 3, D = NBUF - 1;
-  constexpr int NS = 2;                                   // store instructions of a tile's epilogue, per wave
+  constexpr int NBUF = StemG::NBUF, D = NBUF - 1, NS = StemG::NS;
   extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
   u32x4* const wimg = smem;                               // [CO][kSWRow]
   u32x4* const pbuf = smem + kDThreads;                   // the patch ring
@@ -366,15 +298,8 @@ conv_stem_kernel(const ConvK p, const DirK q) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) { s1[a][r] = 0.f; s2[a][r] = 0.f; }
   const __amdgpu_buffer_rsrc_t yr = make_rsrc(p.y, p.y_bytes);
-  float sc8[8], sh8[8];
-  if constexpr (EV == 3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = 8 * fch + j;
-      sc8[j] = (p.scale && c < p.C_out) ? p.scale[c] : 1.f;
-      sh8[j] = (p.shiftv && c < p.C_out) ? p.shiftv[c] : 0.f;
-    }
-  }
+  DirAffine<NA> af;
+  direct_affine_load<EV, NA>(p, 0, p.C_out, fch, af);
   // this lane's patch slots: K step j multiplies tap min(4 j + fch, 8) (taps past 8 meet the filter image's zero chunks) of
   // output pixels (wave, 16 b + frow): input pixel (2 wave + r, 2 (16 b + frow) + s)
   int poff[3][2];
@@ -422,38 +347,9 @@ conv_stem_kernel(const ConvK p, const DirK q) {
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int ow = tw * kDTW + b * 16 + frow;
-        const int c0 = 8 * fch;
-        const bool ok = oh < q.H_out && ow < p.W_out && c0 < p.C_out;
+        const bool pv = oh < q.H_out && ow < p.W_out;
         const int pix_off = img * p.y_img_stride + (oh * p.W_out + ow) * p.ldy;
-        unsigned h8[8];
-        float v8[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v8[r] = acc[0][b][r]; v8[4 + r] = acc[1][b][r]; }
-        if constexpr (EV == 3) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v8[j] = v8[j] * sc8[j] + sh8[j];
-          if (p.relu) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v8[j] = relu_f(v8[j]);
-          }
-        }
-        unsigned h2[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) h2[j] = pack2bf(v8[2 * j], v8[2 * j + 1]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h8[j] = (j & 1) ? (h2[j >> 1] >> 16) : (h2[j >> 1] & 0xffffu);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{h2[0], h2[1], h2[2], h2[3]},
-                                               yr, ok ? (int)((pix_off + c0) * 2) : (int)kOOB, 0, 0);
-        if constexpr (EV == 1) {
-          if (ok) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float f0 = bf2f((unsigned short)h8[r]), f1 = bf2f((unsigned short)h8[4 + r]);
-              s1[0][r] += f0; s2[0][r] += f0 * f0;
-              s1[1][r] += f1; s2[1][r] += f1 * f1;
-            }
-          }
-        }
+        direct_store_pixel<EV>(p, yr, acc, b, pv, pix_off, 0, p.C_out, fch, af, s1, s2);
       }
     }
     if (more) {
@@ -490,27 +386,9 @@ conv_stem_kernel(const ConvK p, const DirK q) {
   }
 }
 
-constexpr int stem_lds() {
-  constexpr int PCH = kSPH * kSPW, PBUF = (PCH + kDThreads - 1) / kDThreads * kDThreads;
-  return (kDThreads + 3 * PBUF) * 16 + 8 * 32 * 2 * 4;
-}
-
 int launch_stem(const ConvK& k, const DirK& q, int grid, hipStream_t s) {
-  constexpr int lds = stem_lds();
-  static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr[3] = {false, false, false};
-  const int ev = k.epi == MBX_EPI_AFFINE ? 2 : k.stats ? 1 : 0;
-  if (!attr[ev]) {
-    if (ev == 2) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else if (ev) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr[ev] = true;
-  }
-  if (ev == 2) hipLaunchKernelGGL((conv_stem_kernel<3>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else if (ev) hipLaunchKernelGGL((conv_stem_kernel<1>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else hipLaunchKernelGGL((conv_stem_kernel<0>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
+  static_assert(StemG::LDS_BYTES <= 160 * 1024, "LDS");
+  return launch_by_ev(k, q, grid, kDThreads, StemG::LDS_BYTES, s, [](auto ev) { return conv_stem_kernel<decltype(ev)::value>; });
 }
 
 // ------------------------------------------------------------------------------------------ whole-width tiles
@@ -529,19 +407,30 @@ constexpr int kWMaxPix = 340;                             // patch pixels a buff
 template <int C8>
 __device__ __forceinline__ int wkey(int pcol) { return C8 == 4 ? ((pcol >> 2) & 3) : C8 == 8 ? ((pcol >> 1) & 7) : 0; }
 
+template <int C8, int CO>
+struct DwG {
+  static constexpr int CI = 8 * C8, NA = CO / 16, NG = (9 * C8 + 3) / 4;
+  static constexpr int PROUNDS = (kWMaxPix * C8 + kDThreads - 1) / kDThreads;
+  static constexpr int PBUF = PROUNDS * kDThreads;
+  static constexpr int WROW = 4 * NG + 1;                 // chunks per filter-image row: the K range, zero fill, one of padding
+  static constexpr int WCH = CO * WROW;
+  static constexpr int WROUNDS = (WCH + kDThreads - 1) / kDThreads;
+  static constexpr int NBUF = 2;                          // two patch buffers, the loads one tile ahead
+  static constexpr int NS = direct_stores(CO);
+  static constexpr int LDS_BYTES = (WROUNDS * kDThreads + NBUF * PBUF) * 16 + 8 * CO * 2 * 4;   // filter image, ring, red
+};
+
+// (The epilogue is this kernel's own text, not direct_store_pixel: with it two data-gradient instantiations took 12 and 28
+// more registers -- LAB_NOTES.md.  The tile loop is conv_direct3_kernel's at two buffers: `ahead` is `more`, no first-tile case.)
 template <int C8, int CO, int EV>
 __device__ __forceinline__ void directw_body(const ConvK& p, const DirW& q, const int first, const int G) {
-  constexpr int CI = 8 * C8, NA = CO / 16, NG = (9 * C8 + 3) / 4;
-  constexpr int PROUNDS = (kWMaxPix * C8 + kDThreads - 1) / kDThreads;
-  constexpr int PBUF = PROUNDS * kDThreads;
-  constexpr int WROW = 4 * NG + 1;                        // chunks per filter-image row: the K range, zero fill, one of padding
-  constexpr int WCH = CO * WROW;
-  constexpr int WROUNDS = (WCH + kDThreads - 1) / kDThreads;
-  constexpr int NS = 2 * (CO / 32 + (CO % 32 ? 1 : 0));   // store instructions of a tile's epilogue, per wave
+  using Geo = DwG<C8, CO>;
+  constexpr int CI = Geo::CI, NA = Geo::NA, NG = Geo::NG, PROUNDS = Geo::PROUNDS, PBUF = Geo::PBUF;
+  constexpr int WROW = Geo::WROW, WCH = Geo::WCH, WROUNDS = Geo::WROUNDS, NS = Geo::NS;
   extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
   u32x4* const wimg = smem;
   u32x4* const pbuf = smem + WROUNDS * kDThreads;         // two patch buffers
-  float* const red = reinterpret_cast<float*>(pbuf + 2 * PBUF);
+  float* const red = reinterpret_cast<float*>(pbuf + Geo::NBUF * PBUF);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = wave_id();
@@ -766,19 +655,11 @@ __device__ __forceinline__ void directw_body(const ConvK& p, const DirW& q, cons
   }
 }
 
-template <int C8, int CO>
-constexpr int directw_lds_bytes() {
-  constexpr int NG = (9 * C8 + 3) / 4, WROW = 4 * NG + 1;
-  constexpr int PBUF = (kWMaxPix * C8 + kDThreads - 1) / kDThreads * kDThreads;
-  constexpr int WB = (CO * WROW + kDThreads - 1) / kDThreads * kDThreads;
-  return (WB + 2 * PBUF) * 16 + 8 * CO * 2 * 4;
-}
-
 // data gradients: the BN backward of the layers whose activation gradient a whole-width launch wrote, as its tail (fused_bn.h)
 template <int C8, int CO>
 __device__ __forceinline__ void directw_bwd_tail(const ConvK& p, const DirW& q, const int first, const int G) {
   extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
-  static_assert(kDThreads * 68 + sizeof(FbShared) <= directw_lds_bytes<C8, CO>(), "the tail's reduce area fits");
+  static_assert(kDThreads * 68 + sizeof(FbShared) <= DwG<C8, CO>::LDS_BYTES, "the tail's reduce area fits");
   const int HW = q.H_out * p.W_out;
   fused_bwd_tail<kDThreads, false>(p, smem, [&](auto&& fn) {
     for (int t = first; t < q.ntiles; t += G) {
@@ -798,30 +679,9 @@ conv_directw_kernel(const ConvK p, const DirW q) {
 }
 
 template <int C8, int CO>
-constexpr int directw_lds() {
-  constexpr int NG = (9 * C8 + 3) / 4, WROW = 4 * NG + 1;
-  constexpr int PBUF = (kWMaxPix * C8 + kDThreads - 1) / kDThreads * kDThreads;
-  constexpr int WB = (CO * WROW + kDThreads - 1) / kDThreads * kDThreads;
-  return (WB + 2 * PBUF) * 16 + 8 * CO * 2 * 4;
-}
-
-template <int C8, int CO>
 int launch_directw(const ConvK& k, const DirW& q, int grid, hipStream_t s) {
-  constexpr int lds = directw_lds<C8, CO>();
-  static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr[3] = {false, false, false};
-  const int ev = k.epi == MBX_EPI_AFFINE ? 2 : k.stats ? 1 : 0;
-  if (!attr[ev]) {
-    if (ev == 2) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_directw_kernel<C8, CO, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else if (ev) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_directw_kernel<C8, CO, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_directw_kernel<C8, CO, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr[ev] = true;
-  }
-  if (ev == 2) hipLaunchKernelGGL((conv_directw_kernel<C8, CO, 3>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else if (ev) hipLaunchKernelGGL((conv_directw_kernel<C8, CO, 1>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else hipLaunchKernelGGL((conv_directw_kernel<C8, CO, 0>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
+  static_assert(DwG<C8, CO>::LDS_BYTES <= 160 * 1024, "LDS");
+  return launch_by_ev(k, q, grid, kDThreads, DwG<C8, CO>::LDS_BYTES, s, [](auto ev) { return conv_directw_kernel<C8, CO, decltype(ev)::value>; });
 }
 
 // tile height of the whole-width launch for an output W_out wide (0: the map is too wide for it)
@@ -834,30 +694,9 @@ inline int directw_th(int W_out) {
 }
 
 template <int CI, int CO>
-constexpr int direct3_lds() {
-  constexpr int C8 = CI / 8;
-  constexpr int PCH = kDPH * kDPW * C8, PBUF = (PCH + kDThreads - 1) / kDThreads * kDThreads;
-  constexpr int WCH = 9 * CO * C8, WB = (WCH + kDThreads - 1) / kDThreads * kDThreads;
-  return (WB + (CI == 32 ? 3 : 2) * PBUF) * 16 + 8 * CO * 2 * 4;
-}
-
-template <int CI, int CO>
 int launch_direct3(const ConvK& k, const DirK& q, int grid, hipStream_t s) {
-  constexpr int lds = direct3_lds<CI, CO>();
-  static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr[3] = {false, false, false};
-  const int ev = k.epi == MBX_EPI_AFFINE ? 2 : k.stats ? 1 : 0;
-  if (!attr[ev]) {
-    if (ev == 2) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct3_kernel<CI, CO, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else if (ev) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct3_kernel<CI, CO, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct3_kernel<CI, CO, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr[ev] = true;
-  }
-  if (ev == 2) hipLaunchKernelGGL((conv_direct3_kernel<CI, CO, 3>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else if (ev) hipLaunchKernelGGL((conv_direct3_kernel<CI, CO, 1>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  else hipLaunchKernelGGL((conv_direct3_kernel<CI, CO, 0>), dim3(grid), dim3(kDThreads), lds, s, k, q);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
+  static_assert(D3G<CI, CO>::LDS_BYTES <= 160 * 1024, "LDS");
+  return launch_by_ev(k, q, grid, kDThreads, D3G<CI, CO>::LDS_BYTES, s, [](auto ev) { return conv_direct3_kernel<CI, CO, decltype(ev)::value>; });
 }
 
 }  // namespace
@@ -881,9 +720,7 @@ int mbx_directw_grid(int N, int H_out, int W_out) {
 // mbx_conv_desc.tile_config = MBX_TILE_DIRECTW: the whole-width direct 3x3 launch (conv_directw_kernel) -- 3x3 / stride 1, forward or data
 // gradient, C_in 32 / 48 / 64, C_out <= 64 (a multiple of 8), maps 8..64 wide; bf16 store with or without statistics, or affine.
 int mbx_launch_directw(ConvK& k, int N, int H_out, hipStream_t s) {
-  if (k.R != 3 || k.S != 3 || k.mul != 1 || k.shift || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits ||
-      k.rscale != 0.f || k.bw_n || (k.epi == MBX_EPI_AFFINE && k.stats))
-    return MBX_ERR_UNSUPPORTED;
+  if (k.R != 3 || k.S != 3 || k.mul != 1 || k.shift || !store_or_affine_only(k)) return MBX_ERR_UNSUPPORTED;
   if ((k.C_in != 32 && k.C_in != 48 && k.C_in != 64) || k.C_out > 64 || k.C_out % 8 || k.pad_t < 0 || k.pad_t > 2 || k.pad_l < 0 || k.pad_l > 2)
     return MBX_ERR_UNSUPPORTED;
   DirW q;
@@ -909,28 +746,11 @@ int mbx_launch_directw(ConvK& k, int N, int H_out, hipStream_t s) {
 // (forward, or the data gradient of one) with C_in in {32, 64}, C_out <= 64 (a multiple of 8) and a bf16 store epilogue
 // with or without statistics, or the affine (+ relu) epilogue of a folded batch norm.
 int mbx_launch_direct3(ConvK& k, int N, int H_out, hipStream_t s) {
-  if (k.mul == 2 && !k.shift && k.C_in == 8) {
-    // the network's first layer (forward only: stride 2, packed RGB input): conv_stem_kernel
-    if (k.R != 3 || k.S != 3 || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits || k.rscale != 0.f || k.bw_n ||
-        (k.epi == MBX_EPI_AFFINE && k.stats) || k.C_out > 32 || k.C_out % 8 || k.pad_t < 0 || k.pad_t > 2 || k.pad_l < 0 || k.pad_l > 2 ||
-        k.Ktot != 72)
-      return MBX_ERR_UNSUPPORTED;
-    DirK q;
-    q.N = N; q.H_out = H_out;
-    q.tiles_h = (H_out + kDTH - 1) / kDTH;
-    q.tiles_w = (k.W_out + kDTW - 1) / kDTW;
-    const long nt = (long)N * q.tiles_h * q.tiles_w;
-    if (nt >= (1L << 30)) return MBX_ERR_UNSUPPORTED;
-    q.ntiles = (int)nt;
-    if (k.dry) return MBX_OK;
-    k.stats_cap = stats_cap_for(mbx_direct3_grid(N, H_out, k.W_out));
-    return launch_stem(k, q, mbx_direct3_grid(N, H_out, k.W_out), s);
-  }
-  if (k.R != 3 || k.S != 3 || k.mul != 1 || k.shift || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits ||
-      k.rscale != 0.f || k.bw_n || (k.epi == MBX_EPI_AFFINE && k.stats))
-    return MBX_ERR_UNSUPPORTED;
-  if ((k.C_in != 32 && k.C_in != 64) || k.C_out > 64 || k.C_out % 8 || k.pad_t < 0 || k.pad_t > 2 || k.pad_l < 0 || k.pad_l > 2 ||
-      (k.C_in == 64 && k.C_out > 48))
+  // the network's first layer (forward only: stride 2, packed RGB input): conv_stem_kernel
+  const bool stem = k.mul == 2 && !k.shift && k.C_in == 8;
+  if (k.R != 3 || k.S != 3 || (!stem && (k.mul != 1 || k.shift)) || !store_or_affine_only(k)) return MBX_ERR_UNSUPPORTED;
+  if (k.C_out % 8 || k.pad_t < 0 || k.pad_t > 2 || k.pad_l < 0 || k.pad_l > 2) return MBX_ERR_UNSUPPORTED;
+  if (stem ? (k.C_out > 32 || k.Ktot != 72) : ((k.C_in != 32 && k.C_in != 64) || k.C_out > 64 || (k.C_in == 64 && k.C_out > 48)))
     return MBX_ERR_UNSUPPORTED;
   DirK q;
   q.N = N; q.H_out = H_out;
@@ -942,6 +762,7 @@ int mbx_launch_direct3(ConvK& k, int N, int H_out, hipStream_t s) {
   const int grid = mbx_direct3_grid(N, H_out, k.W_out);
   k.stats_cap = stats_cap_for(grid);
   if (k.dry) return MBX_OK;
+  if (stem) return launch_stem(k, q, grid, s);
   const int co = k.C_out <= 32 ? 32 : k.C_out <= 48 ? 48 : 64;
   if (k.C_in == 32) {
     if (co == 32) return launch_direct3<32, 32>(k, q, grid, s);

@@ -15,7 +15,7 @@
 // lane group fch holding channels 8 (4 j + fch) .. + 8, filter rows as the A operand -- the accumulation sequence of every
 // output element is the igemm kernels', so the results are bit-identical (tests/test_gpu_conv.py::test_conv_resident).
 // Epilogues: bf16 store (EV = 0), store + batch-norm statistics (EV = 1: statistics row = the image), affine + relu (EV = 3).
-#include "conv_common.h"
+#include "direct_epilogue.h"
 #ifndef MBX_RES_EALL
 #define MBX_RES_EALL 0
 #endif
@@ -91,12 +91,7 @@ __device__ __forceinline__ void wait_vmcnt_k(const int k) {
   }
 }
 
-// LDS row 16 a + f of a filter slot holds output channel rperm(a, f) of the tile: blocks 2A and 2A + 1 leave a lane EIGHT
-// consecutive channels of one pixel (16-byte stores, conv_igemm3_kernel's order); a trailing unpaired block the plain order
-template <int NB>
-__device__ __forceinline__ int rperm(int a, int f) {
-  return (a < (NB / 2) * 2) ? 32 * (a >> 1) + 8 * (f >> 2) + 4 * (a & 1) + (f & 3) : 16 * a + f;
-}
+// (LDS row 16 a + f of a filter slot holds output channel dperm<16 NB>(a, f) of the tile: direct_epilogue.h)
 
 // scheduling pattern of one K step: the NR LDS reads of the next step's fragments interleaved with the first MFMAs
 template <int NR, int NM, int I = 0>
@@ -134,7 +129,6 @@ conv_resident_kernel(const ConvK p, const ResK q) {
   // taps per publication group: half the ring (the next group lands while this one is multiplied); everything resident: 4
   constexpr int GR = D >= RS ? (RS < 4 ? RS : 4) : (D / 2 > 0 ? D / 2 : 1), G0 = GR < RS ? GR : RS;
   static_assert(D >= RS || D >= 2 * GR || GR == 1, "two groups in the ring");
-  constexpr int NP = NB / 2;                              // paired blocks
   extern __shared__ __attribute__((aligned(16))) u32x4 smem[];
   float* const red = reinterpret_cast<float*>(smem);      // [4 waves][16 NB][2]
   u32x4* const ring = smem + G::RED_CH;                   // [D][SLOTP]
@@ -171,7 +165,7 @@ conv_resident_kernel(const ConvK p, const ResK q) {
       const int row = ci / C8, cs = ci - row * C8;
       const int c = cs ^ rkey<C8>(row);
       wv[i] = row < 16 * NB;
-      rowch[i] = wv[i] ? rperm<NB>(row >> 4, row & 15) : 0;                       // channel within the tile
+      rowch[i] = wv[i] ? dperm<16 * NB>(row >> 4, row & 15) : 0;                       // channel within the tile
       wo[i] = (rowch[i] * RS * (8 * C8) + c * 8) * 2;
     }
     // The taps of ALL tiles of this workgroup form ONE stream through the ring (tap T of the stream in slot T % D): behind the
@@ -279,23 +273,8 @@ conv_resident_kernel(const ConvK p, const ResK q) {
     MBXR_STAMP(0);
     if (newim) issue_image(im);
     // per-channel scale / shift of the affine epilogue (folded batch norm, detect.py:313-326)
-    float sc8[NP > 0 ? NP : 1][8], sh8[NP > 0 ? NP : 1][8], sc4[4], sh4[4];
-    if constexpr (EV == 3) {
-#pragma unroll
-      for (int A = 0; A < NP; ++A)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int c = cb + 32 * A + 8 * fch + j;
-          sc8[A][j] = (p.scale && c < ce) ? p.scale[c] : 1.f;
-          sh8[A][j] = (p.shiftv && c < ce) ? p.shiftv[c] : 0.f;
-        }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = cb + 32 * NP + 4 * fch + j;
-        sc4[j] = (p.scale && c < ce) ? p.scale[c] : 1.f;
-        sh4[j] = (p.shiftv && c < ce) ? p.shiftv[c] : 0.f;
-      }
-    }
+    DirAffine<NB> af;
+    direct_affine_load<EV, NB>(p, cb, ce, fch, af);
     if constexpr (EALL) {
 #pragma unroll
       for (int tap = 0; tap < RS; ++tap) tap_rows(tap, E[tap]);
@@ -369,8 +348,7 @@ conv_resident_kernel(const ConvK p, const ResK q) {
     }
 
     MBXR_STAMP(2);
-    // ---- epilogue: blocks 2A, 2A + 1 -> 8 consecutive channels (cb + 32 A + 8 fch ..) of the lane's pixel: 16-byte stores;
-    // an unpaired last block: 4 consecutive channels (cb + 32 NP + 4 fch ..), 8-byte stores
+    // ---- epilogue (direct_epilogue.h): the lane's pixel of each block, the tile's channels [cb, ce)
     float s1[NB][4], s2[NB][4];
 #pragma unroll
     for (int a = 0; a < NB; ++a)
@@ -380,61 +358,7 @@ conv_resident_kernel(const ConvK p, const ResK q) {
 #pragma unroll
     for (int f = 0; f < MI; ++f) {
       const bool pv = opix[f] >= 0;
-      const int pix_off = yo + (pv ? opix[f] : 0) * p.ldy;
-#pragma unroll
-      for (int A = 0; A < NP; ++A) {
-        const int c0 = cb + 32 * A + 8 * fch;
-        const bool ok = pv && c0 < ce;                    // CPT % 8 == 0: a group of eight is all in or all out
-        float v8[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v8[r] = acc[2 * A][f][r]; v8[4 + r] = acc[2 * A + 1][f][r]; }
-        if constexpr (EV == 3) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v8[j] = v8[j] * sc8[A][j] + sh8[A][j];
-          if (p.relu) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v8[j] = relu_f(v8[j]);
-          }
-        }
-        unsigned h2[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) h2[j] = pack2bf(v8[2 * j], v8[2 * j + 1]);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{h2[0], h2[1], h2[2], h2[3]}, yr, ok ? (int)((pix_off + c0) * 2) : (int)kOOB, 0, 0);
-        if constexpr (EV == 1) {
-          if (ok) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const unsigned w0 = h2[r >> 1], w1 = h2[2 + (r >> 1)];
-              const float f0 = (r & 1) ? bf_hi(w0) : bf_lo(w0), f1 = (r & 1) ? bf_hi(w1) : bf_lo(w1);
-              s1[2 * A][r] += f0; s2[2 * A][r] += f0 * f0;
-              s1[2 * A + 1][r] += f1; s2[2 * A + 1][r] += f1 * f1;
-            }
-          }
-        }
-      }
-      if constexpr (NB > 2 * NP) {
-        constexpr int a = 2 * NP;
-        const int c0 = cb + 16 * a + 4 * fch;
-        const bool ok = pv && c0 < ce;
-        float v4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = acc[a][f][r];
-          if constexpr (EV == 3) { v = v * sc4[r] + sh4[r]; if (p.relu) v = relu_f(v); }
-          v4[r] = v;
-        }
-        const unsigned g2[2] = {pack2bf(v4[0], v4[1]), pack2bf(v4[2], v4[3])};
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{g2[0], g2[1]}, yr, ok ? (int)((pix_off + c0) * 2) : (int)kOOB, 0, 0);
-        if constexpr (EV == 1) {
-          if (ok) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float fv = (r & 1) ? bf_hi(g2[r >> 1]) : bf_lo(g2[r >> 1]);
-              s1[a][r] += fv; s2[a][r] += fv * fv;
-            }
-          }
-        }
-      }
+      direct_store_pixel<EV>(p, yr, acc, f, pv, yo + (pv ? opix[f] : 0) * p.ldy, cb, ce, fch, af, s1, s2);
     }
     if constexpr (EV == 1) {
       // ONE statistics row per image: lane sums -> the 16 lanes that share its channels (DPP row sums, eight at a time) -> the
@@ -452,7 +376,7 @@ conv_resident_kernel(const ConvK p, const ResK q) {
           if (frow == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int ch = rperm<NB>(a, 4 * fch + r);
+              const int ch = dperm<16 * NB>(a, 4 * fch + r);
               red[(wave * 16 * NB + ch) * 2] = u[r];
               red[(wave * 16 * NB + ch) * 2 + 1] = u[4 + r];
             }
@@ -585,8 +509,8 @@ conv_pwres_kernel(const ConvK p, const PwK q) {
       const int ci = (lw + kRLW * i) * 64 + lane;
       const int row = ci / C8S, cs = ci - row * C8S;
       const int c = cs ^ rkey<C8S>(row);
-      // LDS row 32 w + 16 a + f = channel 32 w + rperm<2>(a, f) of the column tile (wave w's 32 channels, igemm3's order)
-      chn[i] = 32 * (row >> 5) + rperm<2>((row >> 4) & 1, row & 15);
+      // LDS row 32 w + 16 a + f = channel 32 w + dperm<32>(a, f) of the column tile (wave w's 32 channels, igemm3's order)
+      chn[i] = 32 * (row >> 5) + dperm<32>((row >> 4) & 1, row & 15);
       wo[i] = (chn[i] * (8 * C8) + c * 8) * 2;
     }
     for (int u = first; u < q.nunits; u += G_) {
@@ -771,19 +695,7 @@ int launch_resident(const ConvK& k, const ResK& q, int grid, hipStream_t s) {
   static_assert(lds <= 160 * 1024, "LDS");
   static_assert((G::depth(HWC) - 1) * G::PT < 64, "vmcnt");
   static_assert(HWC <= G::HWMAX, "pixel slots");
-  static bool attr[3] = {false, false, false};
-  const int ev = k.epi == MBX_EPI_AFFINE ? 2 : k.stats ? 1 : 0;
-  if (!attr[ev]) {
-    if (ev == 2) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_resident_kernel<C8, NB, RS, MI, HWC, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else if (ev) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_resident_kernel<C8, NB, RS, MI, HWC, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_resident_kernel<C8, NB, RS, MI, HWC, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr[ev] = true;
-  }
-  if (ev == 2) hipLaunchKernelGGL((conv_resident_kernel<C8, NB, RS, MI, HWC, 3>), dim3(grid), dim3(kRThreads), lds, s, k, q);
-  else if (ev) hipLaunchKernelGGL((conv_resident_kernel<C8, NB, RS, MI, HWC, 1>), dim3(grid), dim3(kRThreads), lds, s, k, q);
-  else hipLaunchKernelGGL((conv_resident_kernel<C8, NB, RS, MI, HWC, 0>), dim3(grid), dim3(kRThreads), lds, s, k, q);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
+  return launch_by_ev(k, q, grid, kRThreads, lds, s, [](auto ev) { return conv_resident_kernel<C8, NB, RS, MI, HWC, decltype(ev)::value>; });
 }
 
 // channel groups per image and 16-channel blocks per group for C_out output channels: four groups (N = 64 images -> one
@@ -804,9 +716,7 @@ int mbx_resident_rows(int N) { return N; }
 // (17 x 17) with C_in 128 / 160 / 192, or of 3 taps on an 8 x 8 map with C_in 192 / 224 / 256; C_out a multiple of 8 and a bf16 store epilogue with or without statistics, or
 // the affine (+ relu) epilogue of a folded batch norm.
 int mbx_launch_resident(ConvK& k, int N, int H_out, hipStream_t s) {
-  if (k.mul != 1 || k.shift || (k.epi != MBX_EPI_STORE && k.epi != MBX_EPI_AFFINE) || k.accumulate || k.skip || k.bits || k.rscale != 0.f ||
-      k.bw_n || (k.epi == MBX_EPI_AFFINE && k.stats))
-    return MBX_ERR_UNSUPPORTED;
+  if (k.mul != 1 || k.shift || !store_or_affine_only(k)) return MBX_ERR_UNSUPPORTED;
   if (k.H_in != H_out || k.W_in != k.W_out || k.C_out % 8 || k.pad_t < 0 || k.pad_l < 0 || k.pad_t >= k.R || k.pad_l >= k.S)
     return MBX_ERR_UNSUPPORTED;
   ResK q;

@@ -139,31 +139,25 @@ def test_conv_epilogues(T):
     assert ok, "accumulate: " + msg
 
 
-@pytest.mark.parametrize("g", [("d1", 2, 37, 45, 32, 32, 3, 3, 1, (0, 0, 0, 0)), ("d2", 3, 41, 33, 32, 64, 3, 3, 1, (1, 1, 1, 1)),
-                               ("d3", 2, 35, 35, 32, 48, 3, 3, 1, (1, 1, 1, 1)), ("d4", 2, 29, 50, 64, 32, 3, 3, 1, (1, 1, 1, 1)),
-                               ("d5", 1, 20, 70, 64, 48, 3, 3, 1, (1, 1, 1, 1)), ("d6", 2, 24, 24, 32, 40, 3, 3, 1, (1, 1, 1, 1)),
-                               ("d7", 4, 147, 147, 32, 64, 3, 3, 1, (1, 1, 1, 1)), ("d8", 3, 61, 75, 8, 32, 3, 3, 2, (0, 0, 0, 0)),
-                               ("d9", 2, 40, 66, 8, 24, 3, 3, 2, (0, 0, 1, 1)), ("d10", 2, 299, 299, 8, 32, 3, 3, 2, (0, 0, 0, 0))],
-                         ids=["valid_32_32", "same_32_64", "same_32_48", "same_64_32", "same_64_48", "cout_40", "stem_2b",
-                              "first_layer_s2", "first_layer_s2_same_24", "stem_1a"])
-def test_conv_direct3_bit_identical(T, g):
-    """tile_config 96 (round 4, csrc/convd.hip; the last three cases: conv_stem_kernel, the stride-2 first layer on the packed
-    RGB input): the direct 3x3 launch -- a persistent workgroup per CU stages each pixel
-    patch with its halo once and multiplies the nine taps out of LDS -- against the implicit-GEMM launch of the same
-    descriptor: forward with statistics and as a data gradient ("full" padding 2 for a VALID forward), ragged tile edges,
-    more tiles than workgroups.  Same accumulation order: outputs bit-identical, statistics = sums of the stored values (one
-    row per workgroup); slices of wider buffers untouched outside; what it does not cover is refused."""
-    torch = T
+def direct3_forward_with_stats(torch, g, before_launch=None):
+    """Forward with statistics of descriptor g under tile_config 0 (implicit GEMM) and the direct 3x3 launch: outputs
+    bit-identical, statistics = sums of the stored values, slices of wider buffers untouched outside, and within the file's
+    tolerance of the float32 reference.  Returns what the callers go on with: x, w, the input view, the device filter, the
+    last output view and the direct launch's statistics rows (= its grid).  before_launch(grid), if given, is called with
+    that grid before anything is launched (a caller's reason to skip)."""
     import ctypes as C
     from multibox_amd import ops, _lib
     l = _lib.lib()
     name, N, H, W, Ci, Co, R, S, st, pads = g
     x, w = make_case(torch, g, seed=11)
     Ho, Wo = out_hw(H, W, R, S, st, pads)
-    stream = torch.cuda.current_stream().cuda_stream
     xb = ops.View.alloc(N, H, W, Ci + 16, zero=True).slice(8, Ci)
     xb.tensor().copy_(x.to(torch.bfloat16))
     wd = w.to(torch.bfloat16).cuda().contiguous()
+    if before_launch is not None:
+        d = ops.make_desc(xb, wd, Co, R, S, st, pads[0], pads[1], ops.View.alloc(N, Ho, Wo, Co))
+        d.tile_config = ops.DIRECT3_TILE_CONFIG
+        before_launch(ops.conv_stats_rows(d))
     outs = []
     for cfg in (0, ops.DIRECT3_TILE_CONFIG):
         yb = ops.View.alloc(N, Ho, Wo, Co + 24, zero=True).slice(16, Co)
@@ -183,6 +177,31 @@ def test_conv_direct3_bit_identical(T, g):
     assert torch.allclose(outs[0][1], outs[1][1], rtol=1e-5, atol=1e-3)
     ok, msg = close(torch, outs[1][0], ref_conv(torch, x, w, st, pads))
     assert ok, msg
+    return x, w, xb, wd, yb, rows
+
+
+@pytest.mark.parametrize("g", [("d1", 2, 37, 45, 32, 32, 3, 3, 1, (0, 0, 0, 0)), ("d2", 3, 41, 33, 32, 64, 3, 3, 1, (1, 1, 1, 1)),
+                               ("d3", 2, 35, 35, 32, 48, 3, 3, 1, (1, 1, 1, 1)), ("d4", 2, 29, 50, 64, 32, 3, 3, 1, (1, 1, 1, 1)),
+                               ("d5", 1, 20, 70, 64, 48, 3, 3, 1, (1, 1, 1, 1)), ("d6", 2, 24, 24, 32, 40, 3, 3, 1, (1, 1, 1, 1)),
+                               ("d7", 4, 147, 147, 32, 64, 3, 3, 1, (1, 1, 1, 1)), ("d8", 3, 61, 75, 8, 32, 3, 3, 2, (0, 0, 0, 0)),
+                               ("d9", 2, 40, 66, 8, 24, 3, 3, 2, (0, 0, 1, 1)), ("d10", 2, 299, 299, 8, 32, 3, 3, 2, (0, 0, 0, 0))],
+                         ids=["valid_32_32", "same_32_64", "same_32_48", "same_64_32", "same_64_48", "cout_40", "stem_2b",
+                              "first_layer_s2", "first_layer_s2_same_24", "stem_1a"])
+def test_conv_direct3_bit_identical(T, g):
+    """tile_config 96 (round 4, csrc/convd.hip; the last three cases: conv_stem_kernel, the stride-2 first layer on the packed
+    RGB input): the direct 3x3 launch -- a persistent workgroup per CU stages each pixel
+    patch with its halo once and multiplies the nine taps out of LDS -- against the implicit-GEMM launch of the same
+    descriptor: forward with statistics and as a data gradient ("full" padding 2 for a VALID forward), ragged tile edges,
+    more tiles than workgroups.  Same accumulation order: outputs bit-identical, statistics = sums of the stored values (one
+    row per workgroup); slices of wider buffers untouched outside; what it does not cover is refused."""
+    torch = T
+    import ctypes as C
+    from multibox_amd import ops, _lib
+    l = _lib.lib()
+    name, N, H, W, Ci, Co, R, S, st, pads = g
+    Ho, Wo = out_hw(H, W, R, S, st, pads)
+    stream = torch.cuda.current_stream().cuda_stream
+    x, w, xb, wd, yb, _ = direct3_forward_with_stats(torch, g)
     # the affine (+ relu) epilogue of a folded batch norm (inference / --fine_tune forward): bit-identical to the implicit GEMM's
     gen = torch.Generator().manual_seed(7)
     scale, shift = (torch.rand(Co, generator=gen) + 0.5).cuda(), (torch.randn(Co, generator=gen) * 0.2).cuda()
@@ -215,6 +234,30 @@ def test_conv_direct3_bit_identical(T, g):
     bad = ops.make_desc(xb, wd, Co, R, S, st, pads[0], pads[1], yb, accumulate=1)
     bad.tile_config = ops.DIRECT3_TILE_CONFIG
     assert l.mbx_conv_supported(C.byref(bad)) == -2
+
+
+@pytest.mark.parametrize("g", [("s1", 30, 50, 130, 32, 48, 3, 3, 1, (1, 1, 1, 1)), ("s2", 30, 50, 130, 64, 32, 3, 3, 1, (1, 1, 1, 1)),
+                               ("s3", 30, 101, 261, 8, 32, 3, 3, 2, (0, 0, 0, 0))],
+                         ids=["direct3_nbuf3", "direct3_nbuf2", "stem"])
+def test_conv_direct_ring_steady_state(T, g):
+    """The steady-state wait of the direct kernels' patch ring (a tile that is neither the workgroup's first nor in its tail) is
+    taken only by a workgroup that walks at least four tiles at two tiles of look-ahead; the cases of
+    test_conv_direct3_bit_identical reach two.  Here 7 x 5 x 30 = 1050 tiles of 8 x 32 (output 50 x 130: ragged right and
+    bottom edges) on 256 workgroups: four and five tiles each.  Forward with statistics, bit-identical to the implicit GEMM.
+    (On a quiet chip a wrong count need not show: test_deep_ring_bit_identical_under_memory_saturation is the proof under load.)"""
+    torch = T
+    name, N, H, W, Ci, Co, R, S, st, pads = g
+    Ho, Wo = out_hw(H, W, R, S, st, pads)
+    ntiles = N * ((Ho + 7) // 8) * ((Wo + 31) // 32)      # the launch's 8 x 32 output tiles
+
+    def walked(grid):                                     # (the library's grid, before anything is launched)
+        ok = ntiles >= 4 * grid + 1 and ntiles % grid != 0
+        if not ok and grid != 256:
+            pytest.skip("%d tiles on %d workgroups: no workgroup with a first, a steady-state and a tail tile and an uneven "
+                        "share (the cases are sized for 256 CUs)" % (ntiles, grid))
+        assert ok, (ntiles, grid)
+
+    direct3_forward_with_stats(torch, g, before_launch=walked)
 
 
 @pytest.mark.parametrize("g,cfg", [(("a1", 3, 35, 35, 64, 96, 3, 3, 1, (1, 1, 1, 1)), 0), (("a2", 2, 17, 17, 128, 160, 1, 7, 1, (0, 3, 0, 3)), 10),

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/disasm.sh conv|wgrad|conv5|nnops|bn|loss|postproc ... -> /tmp/dis/<name>.s (gfx950 ISA of the built object)
+# usage: tools/disasm.sh conv|wgrad|conv5|convd|convr|nnops|bn|loss|postproc ... -> /tmp/dis/<name>.s (gfx950 ISA of the built object)
 set -e
 L=/opt/rocm/lib/llvm/bin
 mkdir -p /tmp/dis

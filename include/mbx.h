@@ -199,6 +199,51 @@ int mbx_loss_fwd_bwd_focal(const float* decoded /*[B,P,4]*/, const float* conf_i
                            int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
                            void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
+/* mbx_loss_fwd_bwd_focal with a CHOICE OF LOCATION TERM (optional, not in the reference, off unless the caller asks): the
+ * one entry for every combination of location term, focal loss and mining.  Every argument but loc_type and loc_beta is
+ * mbx_loss_fwd_bwd_focal's, same order and meaning; gamma == 0 with weights (1, 1) is the plain confidence term,
+ * neg_per_pos != 0 mines.  The confidence side (loss2[1], d_logits, n_neg) does not depend on loc_type.
+ * Per positive prior p of image b (match[b,p] = m >= 0), l = decoded[b,p] and g = gt[b,m], both (x1, y1, x2, y2), L the
+ * positive's term:   loss2[0] = alpha * sum of L over the positives of the batch;
+ *                    d_raw_locs[b,p] = alpha * grad_scale * dL/dl;   (0,0,0,0) for every other prior.
+ * MBX_LOC_L2: L = 1/2 |l - g|^2 -- loss2, d_raw_locs, d_logits and n_neg are byte-identical to mbx_loss_fwd_bwd_focal on
+ * the same remaining arguments (the same float32 lines, the same reduction order).
+ * Every other type is computed in float64: l and g are widened on load, L is accumulated in double, and alpha * grad_scale *
+ * dL/dl is formed in double and rounded to float32 once.
+ * MBX_LOC_SMOOTH_L1: L = sum over the four coordinates of s(|l_k - g_k|), s(d) = d^2 / (2 beta) if d < beta, else
+ *   d - beta / 2 (d == beta is linear); the derivative is (l_k - g_k) / beta or its sign.  beta = loc_beta.
+ * The IoU family first puts the PREDICTION in order (GIoU paper, Algorithm 2): X1 = min(l.x1, l.x2), X2 = max(l.x1, l.x2),
+ * likewise Y1, Y2; the ground-truth box is taken as given (x1 <= x2, y1 <= y2 is the caller's to keep: with such boxes every
+ * output is finite for finite inputs, points, zero-width and zero-area boxes included).  eps = 1e-7 and
+ *   w = X2 - X1, h = Y2 - Y1, gw = g.x2 - g.x1, gh = g.y2 - g.y1
+ *   iw = max(0, min(X2, g.x2) - max(X1, g.x1)), ih likewise, I = iw ih;   U = w h + gw gh - I;   IoU = I / (U + eps)
+ *   cw = max(X2, g.x2) - min(X1, g.x1), ch likewise (the enclosing box)
+ * MBX_LOC_GIOU: L = 1 - IoU + (cw ch - U) / (cw ch + eps)
+ * MBX_LOC_DIOU: L = 1 - IoU + rho2 / (cw^2 + ch^2 + eps), rho2 = ((X1 + X2 - g.x1 - g.x2)^2 + (Y1 + Y2 - g.y1 - g.y2)^2) / 4
+ * MBX_LOC_CIOU: L = DIoU's + a v, v = (4 / pi^2) (atan2(gw, gh) - atan2(w, h))^2, a = v / (1 - IoU + v + eps) held constant
+ *   in the gradient (as in the CIoU paper); d atan2(w, h) = (h dw - w dh) / (w^2 + h^2), 0 where w^2 + h^2 == 0.
+ * Kinks: a min or max takes its first argument at a tie, as written above, and its gradient goes there (so X1's goes to l.x1
+ * when l.x1 <= l.x2, X2's to l.x1 when l.x1 >= l.x2); max(0, .) passes gradient only where its argument is > 0.
+ * mbx_match's cost stays the reference's L2-based one whatever loc_type is; the location term reads the same `match`, so
+ * threshold matching, mining and the focal term compose unchanged.  `alpha` (LOCATION_LOSS_ALPHA, 1000 in the reference)
+ * was sized for L2 on corner residuals: a caller of the IoU types, whose L is of order 1 per positive, sets its own.
+ * An unknown loc_type, a loc_beta that is not finite and > 0 with MBX_LOC_SMOOTH_L1 (it is ignored otherwise), or anything
+ * mbx_loss_fwd_bwd_focal rejects: MBX_ERR_INVALID_ARG; workspace_bytes < mbx_loss_loc_workspace_bytes(B, P):
+ * MBX_ERR_WORKSPACE (a bad argument is reported first); nothing is launched or written either way.  Two launches on
+ * `stream`, one workgroup per image, graph-capturable, the same bytes on every call.
+ * What any of these location terms does to AP on real data is NOT measured here: no trained model or dataset is at hand. */
+enum { MBX_LOC_L2 = 0, MBX_LOC_SMOOTH_L1 = 1, MBX_LOC_GIOU = 2, MBX_LOC_DIOU = 3, MBX_LOC_CIOU = 4 };
+size_t mbx_loss_loc_workspace_bytes(int B, int P);
+int mbx_loss_fwd_bwd_loc(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B,P]*/,
+                         int conf_is_logit, const float* gt /*[B,G,4]*/,
+                         const int32_t* match /*[B,P]*/, float alpha, float grad_scale, int B, int P,
+                         int G, float* loss2 /*[2]*/,
+                         float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
+                         int loc_type /*MBX_LOC_*/, float loc_beta /*MBX_LOC_SMOOTH_L1 only*/,
+                         float gamma, float w_pos, float w_neg,
+                         int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
+                         void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
 /* ------------------------------------------------- detect post-processing (A9-A12)
  * Replaces the per-patch numpy loop detect.py:408-436: decode + clip [0,1]
  * (412-413), filter_proposals (74-104, strict inequalities), sort by confidence

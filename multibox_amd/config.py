@@ -1,5 +1,7 @@
 """config.yaml loader -- same keys as the reference (config.py:6-12, config.yaml.example:1-151),
 attribute access like its EasyDict (easydict itself is not installed here)."""
+import ctypes
+
 import yaml
 
 
@@ -101,3 +103,32 @@ def focal_loss(cfg):
     if alpha is not None and not (number(alpha) and 0 < alpha < 1):
         raise ValueError("LOSS_FOCAL_ALPHA must be a number inside (0, 1), got %r" % (alpha,))
     return float(gamma), (None if alpha is None else float(alpha))
+
+
+LOC_LOSS_TYPES = ("l2", "smooth_l1", "giou", "diou", "ciou")      # MBX_LOC_L2 = 0 .. MBX_LOC_CIOU = 4 (include/mbx.h)
+
+
+def loc_loss(cfg):
+    """The location term of a positive (mbx_loss_fwd_bwd_loc; the reference has L2 alone, so off when absent): None, or
+    (type, beta_or_None) from LOSS_LOC_TYPE (one of l2, smooth_l1, giou, diou, ciou; absent or null = off, the reference's
+    L2 through the entry the other keys choose) and LOSS_LOC_BETA (a number that is finite and > 0 as a float32, default
+    0.1; only with smooth_l1, where it is the residual at which the term turns from quadratic to linear -- beta is None
+    for every other type).  The match keeps the reference's L2-based cost.  LOCATION_LOSS_ALPHA's default of 1000 was
+    sized for L2: with giou, diou or ciou, whose term is of order 1 per positive, set your own.  A value that is no such
+    string, a bool, a list, a NaN, an infinity or a beta <= 0 raises ValueError naming the key.  Host code only."""
+    kind, beta = cfg.get("LOSS_LOC_TYPE"), cfg.get("LOSS_LOC_BETA")
+    if kind is None:
+        if beta is not None:
+            raise ValueError("LOSS_LOC_BETA is given without LOSS_LOC_TYPE")
+        return None
+    if not (isinstance(kind, str) and kind in LOC_LOSS_TYPES):
+        raise ValueError("LOSS_LOC_TYPE must be one of %s, got %r" % (", ".join(LOC_LOSS_TYPES), kind))
+    if kind != "smooth_l1":
+        if beta is not None:
+            raise ValueError("LOSS_LOC_BETA goes with LOSS_LOC_TYPE smooth_l1 only, got it with %s" % kind)
+        return kind, None
+    if beta is None:
+        return kind, 0.1
+    if not (isinstance(beta, (int, float)) and not isinstance(beta, bool) and 0 < ctypes.c_float(beta).value < float("inf")):
+        raise ValueError("LOSS_LOC_BETA must be a finite number > 0, got %r" % (beta,))
+    return kind, float(beta)

@@ -1,5 +1,5 @@
 // libmbx: the training side of the box arithmetic -- prior decode, bipartite matching, threshold matching, loss fwd+bwd
-// (plain, with hard-negative mining, focal).  The detection side is postproc.hip.
+// (plain, with hard-negative mining, focal, with a choice of location term).  The detection side is postproc.hip.
 // HBM/latency-bound integer+float kernels; one workgroup per image,
 // wave64 shuffle reductions.  Built with -ffp-contract=off: the float32 cost arithmetic
 // must keep the reference's rounding sequence (loss.py:21-35).
@@ -264,13 +264,114 @@ match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict_
 }
 
 // ---------------------------------------------------------------------- loss
-__global__ void loss_final_kernel(const double* __restrict__ partial, int B, float alpha, float* __restrict__ loss2) {
+// loc_factor: 0.5 where partial[2b] holds sums of squares (L2: alpha * tf.nn.l2_loss), 1 where it holds the terms themselves.
+__global__ void loss_final_kernel(const double* __restrict__ partial, int B, float alpha, double loc_factor,
+                                  float* __restrict__ loss2) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     double a = 0.0, c = 0.0;
     for (int b = 0; b < B; ++b) { a += partial[2 * b]; c += partial[2 * b + 1]; }
-    loss2[0] = alpha * (float)(a * 0.5);                   // alpha * tf.nn.l2_loss
+    loss2[0] = alpha * (float)(a * loc_factor);
     loss2[1] = (float)c;
   }
+}
+
+// ------------------------------------------------------------- location terms
+// The location terms of mbx_loss_fwd_bwd_loc other than L2 (mbx.h has the definitions), in float64 from the widened
+// float32 corners: the term L of one positive and dL/d(l.x1, l.y1, l.x2, l.y2).  Every min / max takes its FIRST argument at
+// a tie and hands its gradient to it; max(0, .) passes gradient only where its argument is > 0.
+//
+// One axis of the IoU family (x or y): the prediction's two coordinates a, b put in order, and every quantity of that axis
+// with its derivative by the ordered pair (lo, hi).
+struct LocAxis {
+  double ext, gext;          // hi - lo of the prediction (w or h), of the ground truth as given (gw or gh)
+  double ov, ov_lo, ov_hi;   // intersection side max(0, min(hi, g.hi) - max(lo, g.lo)), its derivatives
+  double enc, enc_lo, enc_hi;  // enclosing side max(hi, g.hi) - min(lo, g.lo), its derivatives
+  double s;                  // lo + hi - g.lo - g.hi: twice the centre distance
+  bool lo_is_a, hi_is_a;     // lo = min(a, b) is a, hi = max(a, b) is a: where the gradients of lo and hi go
+};
+
+__device__ __forceinline__ LocAxis loc_axis(double a, double b, double glo, double ghi) {
+  LocAxis t;
+  t.lo_is_a = a <= b;
+  t.hi_is_a = a >= b;
+  const double lo = t.lo_is_a ? a : b, hi = t.hi_is_a ? a : b;
+  t.ext = hi - lo;
+  t.gext = ghi - glo;
+  const bool hi_in = hi <= ghi, lo_in = lo >= glo;           // min(hi, g.hi), max(lo, g.lo)
+  const double side = (hi_in ? hi : ghi) - (lo_in ? lo : glo);
+  const bool open = side > 0.0;
+  t.ov = open ? side : 0.0;
+  t.ov_hi = (open && hi_in) ? 1.0 : 0.0;
+  t.ov_lo = (open && lo_in) ? -1.0 : 0.0;
+  const bool hi_out = hi >= ghi, lo_out = lo <= glo;         // max(hi, g.hi), min(lo, g.lo)
+  t.enc = (hi_out ? hi : ghi) - (lo_out ? lo : glo);
+  t.enc_hi = hi_out ? 1.0 : 0.0;
+  t.enc_lo = lo_out ? -1.0 : 0.0;
+  t.s = ((lo + hi) - glo) - ghi;
+  return t;
+}
+
+// loc_type is the same for the whole launch: the switch is wavefront-uniform.  Returns L; (dx1, dy1, dx2, dy2) = dL/dl.
+__device__ __forceinline__ double loc_term(int loc_type, double beta, const float4 lf, const float4 gf, double& dx1,
+                                           double& dy1, double& dx2, double& dy2) {
+  if (loc_type == MBX_LOC_SMOOTH_L1) {
+    const double r0 = (double)lf.x - (double)gf.x, r1 = (double)lf.y - (double)gf.y, r2 = (double)lf.z - (double)gf.z,
+                 r3 = (double)lf.w - (double)gf.w;
+    double L = 0.0;
+    auto side = [&](double r, double& d) {                   // |r| == beta takes the linear branch
+      const double m = fabs(r);
+      if (m < beta) { L += 0.5 * m * m / beta; d = r / beta; }
+      else { L += m - 0.5 * beta; d = r > 0.0 ? 1.0 : -1.0; }
+    };
+    side(r0, dx1); side(r1, dy1); side(r2, dx2); side(r3, dy2);
+    return L;
+  }
+  constexpr double kEps = 1e-7, kPi = 3.14159265358979323846;
+  const LocAxis X = loc_axis((double)lf.x, (double)lf.z, (double)gf.x, (double)gf.z);
+  const LocAxis Y = loc_axis((double)lf.y, (double)lf.w, (double)gf.y, (double)gf.w);
+  const double inter = X.ov * Y.ov;
+  const double uni = X.ext * Y.ext + X.gext * Y.gext - inter;
+  const double ue = uni + kEps, iou = inter / ue;
+  // derivatives by (x lo, x hi, y lo, y hi): of the intersection, of the union, then of 1 - IoU = (IoU dU - dI) / (U + eps)
+  const double i_xl = Y.ov * X.ov_lo, i_xh = Y.ov * X.ov_hi, i_yl = X.ov * Y.ov_lo, i_yh = X.ov * Y.ov_hi;
+  const double u_xl = -Y.ext - i_xl, u_xh = Y.ext - i_xh, u_yl = -X.ext - i_yl, u_yh = X.ext - i_yh;
+  double L = 1.0 - iou;
+  double g_xl = (iou * u_xl - i_xl) / ue, g_xh = (iou * u_xh - i_xh) / ue, g_yl = (iou * u_yl - i_yl) / ue,
+         g_yh = (iou * u_yh - i_yh) / ue;
+  if (loc_type == MBX_LOC_GIOU) {                            // + t, t = (C - U) / (C + eps): dt = (dC - dU - t dC) / (C + eps)
+    const double c = X.enc * Y.enc, ce = c + kEps, t = (c - uni) / ce;
+    const double c_xl = Y.enc * X.enc_lo, c_xh = Y.enc * X.enc_hi, c_yl = X.enc * Y.enc_lo, c_yh = X.enc * Y.enc_hi;
+    L += t;
+    g_xl += (c_xl - u_xl - t * c_xl) / ce;
+    g_xh += (c_xh - u_xh - t * c_xh) / ce;
+    g_yl += (c_yl - u_yl - t * c_yl) / ce;
+    g_yh += (c_yh - u_yh - t * c_yh) / ce;
+  } else {                                                   // DIoU, CIoU: + q, q = rho^2 / D: dq = (d rho^2 - q dD) / D
+    const double dd = X.enc * X.enc + Y.enc * Y.enc + kEps;
+    const double q = (X.s * X.s + Y.s * Y.s) / 4.0 / dd;
+    L += q;
+    g_xl += (0.5 * X.s - q * 2.0 * X.enc * X.enc_lo) / dd;
+    g_xh += (0.5 * X.s - q * 2.0 * X.enc * X.enc_hi) / dd;
+    g_yl += (0.5 * Y.s - q * 2.0 * Y.enc * Y.enc_lo) / dd;
+    g_yh += (0.5 * Y.s - q * 2.0 * Y.enc * Y.enc_hi) / dd;
+    if (loc_type == MBX_LOC_CIOU) {                          // + a v, a held constant
+      const double delta = atan2(X.gext, Y.gext) - atan2(X.ext, Y.ext);
+      const double v = (4.0 / (kPi * kPi)) * delta * delta;
+      const double a = v / (1.0 - iou + v + kEps);
+      L += a * v;
+      const double sq = X.ext * X.ext + Y.ext * Y.ext;
+      if (sq != 0.0) {                                       // d atan2(w, h) = (h dw - w dh) / (w^2 + h^2); 0 at w = h = 0
+        const double k = a * (8.0 / (kPi * kPi)) * delta / sq;
+        const double v_w = -k * Y.ext, v_h = k * X.ext;      // a dv/dw, a dv/dh
+        g_xl -= v_w; g_xh += v_w; g_yl -= v_h; g_yh += v_h;
+      }
+    }
+  }
+  dx1 = (X.lo_is_a ? g_xl : 0.0) + (X.hi_is_a ? g_xh : 0.0);
+  dx2 = (X.lo_is_a ? 0.0 : g_xl) + (X.hi_is_a ? 0.0 : g_xh);
+  dy1 = (Y.lo_is_a ? g_yl : 0.0) + (Y.hi_is_a ? g_yh : 0.0);
+  dy2 = (Y.lo_is_a ? 0.0 : g_yl) + (Y.hi_is_a ? 0.0 : g_yh);
+  return L;
 }
 
 // ------------------------------------------------- loss with hard-negative mining
@@ -367,12 +468,16 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
 // double), which is x; the file is built with -ffp-contract=off, so no product is fused into a sum either.  That is what
 // makes loss_kernel and loss_focal_kernel<false> at gamma = 0, weights (1, 1) agree (loss_mined_kernel and <true> likewise).
 // An unselected negative adds no loss and gets the gradient +0, not 0 * grad_scale: +0 whatever the sign of grad_scale.
-template <bool MINED, bool FOCAL>
+//   LOC_ANY: the location term of a positive is the one `loc_type` names (loc_term above, float64; MBX_LOC_L2 takes the
+//     float32 lines of the other kernels, so that type gives their bytes).  Without LOC_ANY it is L2 at compile time and
+//     loc_type and loc_beta are not read: the four kernels from before the choice keep their code.
+template <bool MINED, bool FOCAL, bool LOC_ANY>
 __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
                                           const float4* __restrict__ gt, const int* __restrict__ match, float alpha,
-                                          float grad_scale, int P, int G, float gamma, float w_pos, float w_neg,
-                                          int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
-                                          float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
+                                          float grad_scale, int P, int G, int loc_type, float loc_beta, float gamma,
+                                          float w_pos, float w_neg, int neg_per_pos, int min_neg,
+                                          double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
+                                          float* __restrict__ d_logits, int* __restrict__ n_neg) {
   constexpr bool kCountPositives = FOCAL && !MINED;
   const int b = blockIdx.x, tid = threadIdx.x;
   unsigned long long cut = 0ull;                             // no key is below 0: every negative counts
@@ -397,10 +502,17 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
       const bool pos = m >= 0;
       if (pos) {
         const float4 l = decoded[i], q = gt[(size_t)b * G + m];
-        const float d0 = __fsub_rn(l.x, q.x), d1 = __fsub_rn(l.y, q.y), d2 = __fsub_rn(l.z, q.z), d3 = __fsub_rn(l.w, q.w);
-        loc_acc += (double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2 + (double)d3 * d3;   // loss.py:100
-        const float a = alpha * grad_scale;
-        dl = make_float4(a * d0, a * d1, a * d2, a * d3);
+        if (!LOC_ANY || loc_type == MBX_LOC_L2) {
+          const float d0 = __fsub_rn(l.x, q.x), d1 = __fsub_rn(l.y, q.y), d2 = __fsub_rn(l.z, q.z), d3 = __fsub_rn(l.w, q.w);
+          loc_acc += (double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2 + (double)d3 * d3;   // loss.py:100
+          const float a = alpha * grad_scale;
+          dl = make_float4(a * d0, a * d1, a * d2, a * d3);
+        } else {
+          double dx1, dy1, dx2, dy2;
+          loc_acc += loc_term(loc_type, (double)loc_beta, l, q, dx1, dy1, dx2, dy2);
+          const double a = (double)alpha * (double)grad_scale;                                // one rounding, at the store
+          dl = make_float4((float)(a * dx1), (float)(a * dy1), (float)(a * dx2), (float)(a * dy2));
+        }
         if (kCountPositives) ++n_pos;
       }
       // The two sides are one expression with c and w exchanged, -wt * base^gamma * log(arg): one logf and one powf for
@@ -445,8 +557,8 @@ loss_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits
             const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
             int P, int G, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
             float* __restrict__ d_logits) {
-  loss_body<false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, 0.0f, 1.0f, 1.0f, 0, 0, partial,
-                          d_locs, d_logits, nullptr);
+  loss_body<false, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
+                                 1.0f, 0, 0, partial, d_locs, d_logits, nullptr);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -454,8 +566,8 @@ loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
                   const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
                   int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
                   float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
-  loss_body<true, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, 0.0f, 1.0f, 1.0f, neg_per_pos,
-                         min_neg, partial, d_locs, d_logits, n_neg);
+  loss_body<true, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
+                                1.0f, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
 }
 
 template <bool MINED>
@@ -465,8 +577,20 @@ loss_focal_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
                   int P, int G, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
                   double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs, float* __restrict__ d_logits,
                   int* __restrict__ n_neg) {
-  loss_body<MINED, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, gamma, w_pos, w_neg, neg_per_pos,
-                         min_neg, partial, d_locs, d_logits, n_neg);
+  loss_body<MINED, true, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, gamma, w_pos,
+                                w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
+}
+
+// mbx_loss_fwd_bwd_loc: loss_focal_kernel<MINED> with the location term chosen at run time.
+template <bool MINED>
+__global__ void __launch_bounds__(kThreads)
+loss_loc_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                int P, int G, int loc_type, float loc_beta, float gamma, float w_pos, float w_neg, int neg_per_pos,
+                int min_neg, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
+                float* __restrict__ d_logits, int* __restrict__ n_neg) {
+  loss_body<MINED, true, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta, gamma, w_pos,
+                               w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
 }
 
 }  // namespace
@@ -533,16 +657,19 @@ extern "C" int mbx_match_extend(const float* priors, const float* gt, const int3
 extern "C" size_t mbx_loss_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 1) * 2 * sizeof(double); }
 extern "C" size_t mbx_loss_mined_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 extern "C" size_t mbx_loss_focal_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+extern "C" size_t mbx_loss_loc_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 
-// What the three loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
+// What the four loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
 // the kernel of `kind`, then loss_final_kernel.  An entry checks its own arguments first; those and the ones here all
-// answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal mines iff neg_per_pos != 0.
-enum class LossKind { kPlain, kMined, kFocal };
+// answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal and loc mine iff neg_per_pos != 0;
+// loc_type is MBX_LOC_L2 for every kind but kLoc.
+enum class LossKind { kPlain, kMined, kFocal, kLoc };
 
 static int launch_loss(LossKind kind, const float* decoded, const float* logits, int conf_is_logit, const float* gt,
                        const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
-                       float* d_raw_locs, float* d_logits, float gamma, float w_pos, float w_neg, int neg_per_pos,
-                       int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes, mbx_stream_t stream) {
+                       float* d_raw_locs, float* d_logits, int loc_type, float loc_beta, float gamma, float w_pos,
+                       float w_neg, int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes,
+                       mbx_stream_t stream) {
   if (!decoded || !logits || !gt || !match || !loss2 || B <= 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < mbx_loss_workspace_bytes(B)) return MBX_ERR_WORKSPACE;
   double* partial = reinterpret_cast<double*>(workspace);
@@ -564,9 +691,15 @@ static int launch_loss(LossKind kind, const float* decoded, const float* logits,
                          mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, gamma, w_pos,
                          w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg);
       break;
+    case LossKind::kLoc:
+      hipLaunchKernelGGL(neg_per_pos ? loss_loc_kernel<true> : loss_loc_kernel<false>, dim3(B), dim3(kThreads), 0,
+                         mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, loc_type, loc_beta,
+                         gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg);
+      break;
   }
   MBX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha, loss2);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha,
+                     loc_type == MBX_LOC_L2 ? 0.5 : 1.0, loss2);
   MBX_LAUNCH_CHECK();
   return MBX_OK;
 }
@@ -576,7 +709,7 @@ extern "C" int mbx_loss_fwd_bwd(const float* decoded, const float* logits, int c
                                 float* d_raw_locs, float* d_logits, void* workspace, size_t workspace_bytes,
                                 mbx_stream_t stream) {
   return launch_loss(LossKind::kPlain, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
-                     d_raw_locs, d_logits, 0.0f, 1.0f, 1.0f, 0, 0, nullptr, workspace, workspace_bytes, stream);
+                     d_raw_locs, d_logits, MBX_LOC_L2, 0.0f, 0.0f, 1.0f, 1.0f, 0, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mbx_loss_fwd_bwd_mined(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
@@ -585,7 +718,15 @@ extern "C" int mbx_loss_fwd_bwd_mined(const float* decoded, const float* logits,
                                       void* workspace, size_t workspace_bytes, mbx_stream_t stream) {
   if (neg_per_pos < 1 || min_neg < 0) return MBX_ERR_INVALID_ARG;
   return launch_loss(LossKind::kMined, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
-                     d_raw_locs, d_logits, 0.0f, 1.0f, 1.0f, neg_per_pos, min_neg, n_neg, workspace, workspace_bytes, stream);
+                     d_raw_locs, d_logits, MBX_LOC_L2, 0.0f, 0.0f, 1.0f, 1.0f, neg_per_pos, min_neg, n_neg, workspace,
+                     workspace_bytes, stream);
+}
+
+// The checks of the focal arguments, shared by mbx_loss_fwd_bwd_focal and mbx_loss_fwd_bwd_loc.
+static bool focal_arguments_ok(float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg) {
+  if (!(gamma >= 0.0f && gamma <= 10.0f)) return false;                                    // a NaN fails both
+  if (!(w_pos >= 0.0f && w_neg >= 0.0f) || isinf(w_pos) || isinf(w_neg)) return false;
+  return !(neg_per_pos < 0 || min_neg < 0 || (neg_per_pos == 0 && min_neg > 0));
 }
 
 extern "C" int mbx_loss_fwd_bwd_focal(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
@@ -593,9 +734,21 @@ extern "C" int mbx_loss_fwd_bwd_focal(const float* decoded, const float* logits,
                                       float* d_raw_locs, float* d_logits, float gamma, float w_pos, float w_neg,
                                       int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes,
                                       mbx_stream_t stream) {
-  if (!(gamma >= 0.0f && gamma <= 10.0f)) return MBX_ERR_INVALID_ARG;                      // a NaN fails both
-  if (!(w_pos >= 0.0f && w_neg >= 0.0f) || isinf(w_pos) || isinf(w_neg)) return MBX_ERR_INVALID_ARG;
-  if (neg_per_pos < 0 || min_neg < 0 || (neg_per_pos == 0 && min_neg > 0)) return MBX_ERR_INVALID_ARG;
+  if (!focal_arguments_ok(gamma, w_pos, w_neg, neg_per_pos, min_neg)) return MBX_ERR_INVALID_ARG;
   return launch_loss(LossKind::kFocal, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
-                     d_raw_locs, d_logits, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace, workspace_bytes, stream);
+                     d_raw_locs, d_logits, MBX_LOC_L2, 0.0f, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
+                     workspace_bytes, stream);
+}
+
+extern "C" int mbx_loss_fwd_bwd_loc(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                    const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
+                                    float* d_raw_locs, float* d_logits, int loc_type, float loc_beta, float gamma, float w_pos,
+                                    float w_neg, int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace,
+                                    size_t workspace_bytes, mbx_stream_t stream) {
+  if (loc_type < MBX_LOC_L2 || loc_type > MBX_LOC_CIOU) return MBX_ERR_INVALID_ARG;
+  if (loc_type == MBX_LOC_SMOOTH_L1 && !(loc_beta > 0.0f && !isinf(loc_beta))) return MBX_ERR_INVALID_ARG;   // a NaN fails
+  if (!focal_arguments_ok(gamma, w_pos, w_neg, neg_per_pos, min_neg)) return MBX_ERR_INVALID_ARG;
+  return launch_loss(LossKind::kLoc, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
+                     workspace_bytes, stream);
 }

@@ -7,9 +7,12 @@ on the caller's stream, graph-capturable.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
+from .config import LOC_LOSS_TYPES as LOC_TYPES
 
 SMALL_EPSILON = 1e-10   # loss.py:6
 
@@ -92,6 +95,30 @@ def _focal_arguments(focal_gamma, focal_alpha):
     return float(focal_gamma), float(focal_alpha), 1.0 - float(focal_alpha)
 
 
+LOC_BETA_DEFAULT = 0.1
+
+
+def _loc_arguments(loc_loss, loc_beta):
+    """None (off), or (loc_type, loc_beta) as mbx_loss_fwd_bwd_loc takes them.  Raises ValueError on a bad value."""
+    if loc_loss is None:
+        if loc_beta is not None:
+            raise ValueError("loc_beta is given without loc_loss")
+        return None
+    if not (isinstance(loc_loss, str) and loc_loss in LOC_TYPES):
+        raise ValueError("loc_loss must be one of %s, got %r" % (", ".join(LOC_TYPES), loc_loss))
+    if loc_loss != "smooth_l1":
+        if loc_beta is not None:
+            raise ValueError("loc_beta goes with loc_loss 'smooth_l1' only, got it with %r" % (loc_loss,))
+        return LOC_TYPES.index(loc_loss), 0.0
+    if loc_beta is None:
+        return LOC_TYPES.index(loc_loss), LOC_BETA_DEFAULT
+    # the entry takes a float32: the value has to be finite and > 0 as one
+    if not (isinstance(loc_beta, (int, float)) and not isinstance(loc_beta, bool)
+            and 0.0 < ctypes.c_float(loc_beta).value < float("inf")):
+        raise ValueError("loc_beta must be a finite number > 0 (as a float32), got %r" % (loc_beta,))
+    return LOC_TYPES.index(loc_loss), float(loc_beta)
+
+
 class MultiboxLoss:
     """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step).
 
@@ -108,11 +135,19 @@ class MultiboxLoss:
     positive's -log c is weighted by w^gamma and a counted negative's -log w by c^gamma (mbx_loss_fwd_bwd_focal,
     include/mbx.h).  focal_alpha (a float inside (0, 1); None = both sides weigh 1; only with focal_gamma) weighs the
     positives by alpha and the negatives by 1 - alpha.  With neg_per_pos the mined negatives are the ones counted, and the
-    extended ``match`` is read as by the other two.  What that does to AP on real data is not measured here either."""
+    extended ``match`` is read as by the other two.  What that does to AP on real data is not measured here either.
+
+    loc_loss (one of LOC_TYPES: "l2", "smooth_l1", "giou", "diou", "ciou"; None = off, the reference's L2 through the entry
+    chosen above): the location term of a positive (mbx_loss_fwd_bwd_loc, include/mbx.h, the one entry for every
+    combination with the three switches above; "l2" gives the reference's bytes through it).  loc_beta (a finite float > 0,
+    default 0.1; only with "smooth_l1") is where smooth-L1 turns from quadratic to linear.  The match keeps the reference's
+    L2-based cost.  location_loss_alpha's 1000 was sized for L2: with an IoU type, whose term is of order 1 per positive,
+    pass your own.  What any of these does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
-                 min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None):
+                 min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None):
         self.focal = _focal_arguments(focal_gamma, focal_alpha)
+        self.loc = _loc_arguments(loc_loss, loc_beta)
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
         self.P = self.priors.shape[0]
         self.B, self.G, self.alpha = int(batch_size), int(max_num_bboxes), float(location_loss_alpha)
@@ -131,7 +166,10 @@ class MultiboxLoss:
             mining = (neg_per_pos, min_neg, self.n_neg.data_ptr())
         # the entry forward_backward calls, the arguments it has between the common ones and the workspace, its workspace
         l = _lib.lib()
-        if self.focal is not None:
+        if self.loc is not None:
+            self.entry, self.entry_args = "mbx_loss_fwd_bwd_loc", self.loc + (self.focal or (0.0, 1.0, 1.0)) + mining
+            ws_bytes = l.mbx_loss_loc_workspace_bytes(self.B, self.P)
+        elif self.focal is not None:
             self.entry, self.entry_args = "mbx_loss_fwd_bwd_focal", self.focal + mining
             ws_bytes = l.mbx_loss_focal_workspace_bytes(self.B, self.P)
         elif neg_per_pos is not None:

@@ -41,16 +41,17 @@ class Trainer:
                  decay_steps_=7116, learning_rate_decay_factor=0.94, staircase=True, rmsprop_decay=0.9,
                  rmsprop_momentum=0.0, rmsprop_epsilon=1.0, moving_average_decay=0.9999, use_graph=True,
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
-                 match_iou_threshold=None, focal_gamma=None, focal_alpha=None):
+                 match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None):
         assert net.mode == "train"
         self.net = net
         self.pg = process_group
         # neg_per_pos / min_neg: hard-negative mining of the confidence loss (MultiboxLoss; None = the reference's loss)
         # match_iou_threshold: threshold matching behind the bipartite match (MultiboxLoss; None = the reference's match alone)
         # focal_gamma / focal_alpha: focal loss on the confidence term (MultiboxLoss; None = the reference's loss)
+        # loc_loss / loc_beta: the location term of a positive (MultiboxLoss; None = the reference's L2)
         self.loss = MultiboxLoss(bbox_priors, net.B, max_num_bboxes, location_loss_alpha, device=net.dev,
                                  neg_per_pos=neg_per_pos, min_neg=min_neg, match_iou_threshold=match_iou_threshold,
-                                 focal_gamma=focal_gamma, focal_alpha=focal_alpha)
+                                 focal_gamma=focal_gamma, focal_alpha=focal_alpha, loc_loss=loc_loss, loc_beta=loc_beta)
         assert self.loss.P == net.P, "priors (%d) do not match the network's predictions (%d)" % (self.loss.P, net.P)
         self.loss.d_locs, self.loss.d_logits = net.d_locs, net.d_logits
         self.lr0, self.dsteps, self.lr_factor, self.staircase = initial_learning_rate, decay_steps_, learning_rate_decay_factor, staircase

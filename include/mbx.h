@@ -937,6 +937,42 @@ int mbx_rmsprop_ema_step(float* w, const float* g, float* ms, float* mom /*NULL 
 int mbx_ema_update(float* ema, const float* value, int64_t n, float ema_decay, const float* skip_ctl /*as above*/,
                    mbx_stream_t stream);
 
+/* Global-norm gradient clipping and the non-finite-step guard (not in the reference; nothing here runs unless asked for).
+ * The clipped quantity is the vector the optimiser consumes, g' = g + wd*w of mbx_rmsprop_ema_step (g' = g where wd = 0):
+ * what tf.clip_by_global_norm would see on the reference's total_loss, which contains slim's regulariser.  Three steps,
+ * no host synchronisation, no floating-point atomics -- the same inputs give the same bits:
+ *
+ * mbx_grad_sqnorm: partials[b] = sum over the elements workgroup b owns of (double)g'^2, for one flat range of n elements;
+ *   g' is formed in float32 by the optimiser's own device expression, widened, squared and summed in double (per lane, then
+ *   wavefront, then workgroup).  It writes mbx_grad_sqnorm_partials(n) slots (a fixed function of n: ceil(ceil(n/4)/256)
+ *   capped at 2048; lane t of workgroup b owns the 16-byte groups b*256 + t + j * 256 * slots, j = 0, 1, ..., and the same
+ *   stride over the n % 4 tail -- element by element throughout when g or w is not 16-byte aligned).  w must be given when
+ *   wd != 0 and is ignored (may be NULL) when wd == 0.  partials: DEVICE, 8-byte aligned.
+ *
+ * mbx_clip_finalize: one workgroup sums partials[0, n_slots) -- the slots of every range, in a fixed order -- and writes the
+ *   CLIP BLOCK clip[0..8) (DEVICE float32) from total, norm = sqrt(total) and max_norm (> 0; INFINITY = never clip, only
+ *   guard), everything computed in double:
+ *     clip[0] = ctl[0]                      clip[1] = ctl[1] + (total is Inf or NaN ? 1 : 0)
+ *     clip[2] = scale = norm > max_norm ? max_norm / norm : exactly 1.0f   (1.0f for a norm of 0 and for a non-finite total)
+ *     clip[3] = (float)norm, before clipping          clip[4] = norm > max_norm ? 1 : 0          clip[5..8) = 0
+ *   ctl is the step control block (two float32, see mbx_rmsprop_ema_step); it is only read.  Words [0], [1] make the clip
+ *   block a drop-in skip_ctl: every gated launch that is handed the clip block instead of ctl (mbx_rmsprop_ema_step_clipped,
+ *   mbx_bn_moving_update, mbx_ema_update) skips a step with a non-finite gradient exactly as it skips a flagged one.
+ *   counts (DEVICE int64[2]): counts[0] += 1 when the step is clipped, counts[1] += 1 when its total is non-finite; neither
+ *   when ctl was already flagged (that step's gradients are poisoned by design and the skip has its cause).
+ *
+ * mbx_rmsprop_ema_step_clipped: mbx_rmsprop_ema_step with the clip block in the place of skip_ctl (required); the trainable
+ *   branch uses clip[2] * g'.  With clip[2] == 1.0f every result is byte-identical to mbx_rmsprop_ema_step's.              */
+int64_t mbx_grad_sqnorm_partials(int64_t n);
+int mbx_grad_sqnorm(const float* g, const float* w /*NULL if wd == 0*/, int64_t n, float wd, double* partials,
+                    mbx_stream_t stream);
+int mbx_clip_finalize(const double* partials, int64_t n_slots, double max_norm, const float* ctl, float* clip /*[8]*/,
+                      int64_t* counts /*[2]*/, mbx_stream_t stream);
+int mbx_rmsprop_ema_step_clipped(float* w, const float* g, float* ms, float* mom /*NULL if momentum==0*/,
+                                 float* ema /*or NULL*/, void* w_bf16 /*or NULL*/, int64_t n, float lr,
+                                 float decay, float momentum, float eps, float wd, float ema_decay,
+                                 int trainable, float* reg_loss, const float* clip, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ training input augmentation (row F1)
  * The pixel half of the reference's training input graph (inputs.py:264-351: crop, tf.image.resize_images with a
  * random ResizeMethod, distort_color, random_flip_left_right, (image - 0.5) * 2) for one batch.  The host draws every

@@ -103,6 +103,10 @@ _SIGS = {
     "mbx_filter_prepare": (I, [P, P, P, I, I, P]),
     "mbx_rmsprop_ema_step": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, I, P, P, P]),
     "mbx_ema_update": (I, [P, P, C.c_int64, F, P, P]),
+    "mbx_grad_sqnorm_partials": (C.c_int64, [C.c_int64]),
+    "mbx_grad_sqnorm": (I, [P, P, C.c_int64, F, P, P]),
+    "mbx_clip_finalize": (I, [P, C.c_int64, D, P, P, P, P]),
+    "mbx_rmsprop_ema_step_clipped": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, I, P, P, P]),
 }
 
 _lib = None

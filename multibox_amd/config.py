@@ -132,3 +132,18 @@ def loc_loss(cfg):
     if not (isinstance(beta, (int, float)) and not isinstance(beta, bool) and 0 < ctypes.c_float(beta).value < float("inf")):
         raise ValueError("LOSS_LOC_BETA must be a finite number > 0, got %r" % (beta,))
     return kind, float(beta)
+
+
+def grad_clip(cfg):
+    """Global-norm gradient clipping and the non-finite-step guard (mbx_grad_sqnorm / mbx_clip_finalize /
+    mbx_rmsprop_ema_step_clipped; not in the reference, so off when absent): None, or CLIP_GRADIENT_NORM as a float > 0
+    (absent or null = off; .inf = never clip, only skip steps whose gradient is not finite).  The clipped vector is the one
+    the optimiser consumes, g + WEIGHT_DECAY * w over the trainable filters and g over the trainable betas: what
+    tf.clip_by_global_norm would see on the reference's total_loss, which contains slim's regulariser.  A bool, a string, a
+    list, a NaN or a value <= 0 raises ValueError naming the key.  Host code only."""
+    v = cfg.get("CLIP_GRADIENT_NORM")
+    if v is None:
+        return None
+    if not (isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0):
+        raise ValueError("CLIP_GRADIENT_NORM must be a number > 0 (.inf = guard only), got %r" % (v,))
+    return float(v)

@@ -41,7 +41,8 @@ class Trainer:
                  decay_steps_=7116, learning_rate_decay_factor=0.94, staircase=True, rmsprop_decay=0.9,
                  rmsprop_momentum=0.0, rmsprop_epsilon=1.0, moving_average_decay=0.9999, use_graph=True,
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
-                 match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None):
+                 match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
+                 clip_gradient_norm=None):
         assert net.mode == "train"
         self.net = net
         self.pg = process_group
@@ -92,6 +93,25 @@ class Trainer:
         net.defer_moving = True
         self.skipped_steps = torch.zeros((), dtype=torch.int64, device=net.dev)
         self._skipped_seen = 0
+        # clip_gradient_norm: global-norm clipping of the vector the optimiser consumes (g + WEIGHT_DECAY * w over the
+        # trainable filters, g over the trainable betas: what tf.clip_by_global_norm would see on the reference's total_loss,
+        # which contains slim's regulariser) and the non-finite-step guard; inf = guard only; None = the reference's step,
+        # none of the launches below.  The optimiser phase then runs one mbx_grad_sqnorm per trainable range into
+        # consecutive slots of _clip_partials, one mbx_clip_finalize that turns them into the clip block (words [0], [1]:
+        # net.step_ctl plus the non-finite flag -- a drop-in skip_ctl; [2] the scale), and hands the clip block to every
+        # gated launch in the place of net.step_ctl, which itself is never written.
+        self.clip_norm = None
+        if clip_gradient_norm is not None:
+            self.clip_norm = float(clip_gradient_norm)
+            if not self.clip_norm > 0:
+                raise ValueError("clip_gradient_norm must be > 0 (inf = guard only), got %r" % (clip_gradient_norm,))
+            slots = _lib.lib().mbx_grad_sqnorm_partials
+            self._clip_slots = [(int(slots(hi - lo)) if on and hi > lo else 0) for _, lo, hi, on in self.opt_ranges]
+            self._clip_partials = torch.zeros((max(1, sum(self._clip_slots)),), dtype=torch.float64, device=net.dev)
+            self._clip_block = torch.zeros((8,), **f32)
+            self._clip_block[2] = 1.0
+            self._clip_counts = torch.zeros((2,), dtype=torch.int64, device=net.dev)      # [clipped, non-finite] steps
+            self._nonfinite_seen = 0
         # backward segments = gradient buckets (each also ends in one grouped weight-gradient launch and is one hipGraph).
         # Four of 60 MB; data-parallel runs cut the LAST one once more: the 2 M parameters at the bottom of the network
         # (stem, Mixed_5b, block35: 6.7 MB of the 240) get a bucket of their own, so that the all-reduce nothing overlaps
@@ -207,6 +227,9 @@ class Trainer:
             self._skipped_seen += skipped
             ev = {"event": "skipped_steps", "count": skipped, "global_step_before": self.global_step,
                   "global_step": self.global_step - skipped}
+            if getattr(self, "clip_norm", None) is not None:      # how many of them the non-finite guard skipped
+                nf = self.nonfinite_steps()
+                ev["nonfinite_steps"], self._nonfinite_seen = nf - self._nonfinite_seen, nf
             ev.update(note)
             self.events.append(ev)
             self.global_step -= skipped                # only applied steps count
@@ -531,6 +554,8 @@ class Trainer:
         # (net.reg_loss was cleared by the step's mbx_step_begin launch: Net.zero_grads)
         P = lambda t_, off=0: None if t_ is None else t_.data_ptr() + 4 * off
         ctl = net.step_ctl.data_ptr()                  # non-zero -> every launch below is a no-op (poisoned step / stop request)
+        if self.clip_norm is not None:
+            return self._optimizer_clipped(lr, d, s)
         for buf, lo, hi, on in self.opt_ranges:
             n = hi - lo
             if n <= 0:
@@ -546,6 +571,60 @@ class Trainer:
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
         net.apply_moving_update(net.step_ctl, self.skipped_steps, self.MMema, self.MVema, d)
         net.prepare_filters()
+
+    def _optimizer_clipped(self, lr, d, s):
+        """The optimiser phase under clip_gradient_norm: the squared norm of every trainable range, the clip block, then
+        _optimizer's launches through the clipped entry point with the clip block as their gate (frozen ranges too: they
+        skip together).  No allocation, no host synchronisation; every rank computes the same block from the reduced
+        gradients."""
+        net, l = self.net, _lib.lib()
+        P = lambda t_, off=0: None if t_ is None else t_.data_ptr() + 4 * off
+        slot = 0
+        for (buf, lo, hi, on), k in zip(self.opt_ranges, self._clip_slots):
+            if not k:
+                continue
+            part = self._clip_partials.data_ptr() + 8 * slot
+            if buf == "W":
+                _lib.check(l.mbx_grad_sqnorm(P(net.Wg, lo), P(net.W, lo), hi - lo, WEIGHT_DECAY, part, s), "grad_sqnorm W")
+            else:
+                _lib.check(l.mbx_grad_sqnorm(P(net.Btg, lo), None, hi - lo, 0.0, part, s), "grad_sqnorm beta")
+            slot += k
+        _lib.check(l.mbx_clip_finalize(self._clip_partials.data_ptr(), max(1, slot), self.clip_norm, net.step_ctl.data_ptr(),
+                                       self._clip_block.data_ptr(), self._clip_counts.data_ptr(), s), "clip_finalize")
+        clip = self._clip_block.data_ptr()
+        for buf, lo, hi, on in self.opt_ranges:
+            n = hi - lo
+            if n <= 0:
+                continue
+            if buf == "W":
+                _lib.check(l.mbx_rmsprop_ema_step_clipped(P(net.W, lo), P(net.Wg, lo), P(self.Wms, lo), P(self.Wmom, lo), P(self.Wema, lo),
+                                                          net.Wb.data_ptr() + 2 * lo, n, lr, self.rms_decay, self.momentum, self.eps,
+                                                          WEIGHT_DECAY, d, on, net.reg_loss.data_ptr(), clip, s), "rmsprop W (clipped)")
+            else:
+                _lib.check(l.mbx_rmsprop_ema_step_clipped(P(net.Bt, lo), P(net.Btg, lo), P(self.Btms, lo), P(self.Btmom, lo), P(self.Btema, lo),
+                                                          None, n, lr, self.rms_decay, self.momentum, self.eps, 0.0, d, on, None, clip, s),
+                           "rmsprop beta (clipped)")
+        assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
+        net.apply_moving_update(self._clip_block, self.skipped_steps, self.MMema, self.MVema, d)
+        net.prepare_filters()
+
+    def grad_norm(self):
+        """Global norm of the last step's optimiser input before clipping (see clip_gradient_norm), or None without the
+        key -- host sync; call it at logging intervals."""
+        return None if self.clip_norm is None else float(self._clip_block[3])
+
+    def clip_scale(self):
+        """The factor the last step's optimiser input was multiplied by (1.0 = not clipped), or None without the key --
+        host sync."""
+        return None if self.clip_norm is None else float(self._clip_block[2])
+
+    def clipped_steps(self):
+        """Steps clipped so far, or None without the key -- host sync."""
+        return None if self.clip_norm is None else int(self._clip_counts[0])
+
+    def nonfinite_steps(self):
+        """Steps skipped so far because their gradient was not finite, or None without the key -- host sync."""
+        return None if self.clip_norm is None else int(self._clip_counts[1])
 
     def losses(self):
         """(location_loss, confidence_loss, regularization_loss, total_loss) -- host sync."""

@@ -973,6 +973,44 @@ int mbx_rmsprop_ema_step_clipped(float* w, const float* g, float* ms, float* mom
                                  float decay, float momentum, float eps, float wd, float ema_decay,
                                  int trainable, float* reg_loss, const float* clip, mbx_stream_t stream);
 
+/* Optimiser choice: momentum SGD, Adam and AdamW beside RMSProp (not in the reference; nothing here runs unless asked for).
+ * Both entry points are mbx_rmsprop_ema_step with another element rule: one streaming body gives every rule the same gate,
+ * EMA (from the weight before the step), regulariser (reg_loss += wd_l2/2 * sum w^2 when wd_l2 != 0), frozen ranges
+ * (trainable = 0: EMA, regulariser and bf16 refresh only), bf16 refresh and 16-byte accesses where every stream is 16-byte
+ * aligned.  g' = g + wd_l2*w, the optimiser's one device expression.  ctl (DEVICE, may be NULL when clipped == 0): the step
+ * control block; either of its first two words non-zero: the launch does nothing.  clipped != 0: ctl is the CLIP BLOCK of
+ * mbx_clip_finalize (required) and g' = clip[2] * g'; a scale of exactly 1.0f changes no bit.
+ *
+ * mbx_sgd_ema_step (tf.train.MomentumOptimizer): acc = momentum*acc + g' ; w -= lr*acc, or with nesterov != 0
+ *   w -= lr*(g' + momentum*acc).  mom is NULL if and only if momentum == 0: then w -= lr*g' and no slot is read or written.
+ *
+ * mbx_adam_ema_step: m = beta1*m + (1-beta1)*g' ; v = beta2*v + (1-beta2)*g'^2 ;
+ *   w -= lr*((m/bc1) / (sqrt(v/bc2) + eps) + wd_decoupled*w), w the value before the step, bc_i = 1 - beta_i^t.
+ *   wd_decoupled != 0 is AdamW (callers then pass wd_l2 = 0).  t counts APPLIED steps: t = calls + 1 - (skipped ? *skipped : 0),
+ *   calls the host's count of step launches so far and skipped (DEVICE int64, may be NULL) the counter of steps the gate
+ *   skipped, as mbx_bn_moving_update maintains it -- read before this step's own increment, which comes later on the stream.
+ *   The kernel computes both corrections itself, in double: a skipped step never shifts them and the host never synchronises.
+ *   As computed: c_i = (float)(1 / bc_i), the reciprocal formed in double and rounded to float32 once per thread, then per
+ *   element m^ = m*c1, v^ = v*c2 and the step lr*(m^ / (sqrtf(v^) + eps) + wd_decoupled*w) in float32 -- a multiplication by
+ *   the rounded reciprocal in the place of each division by bc_i, one float32 rounding more than the formula above.
+ *   CONTRACT: calls >= *skipped (every skipped step was a launch the host counted).  The device cannot report a count that
+ *   breaks it, so t < 1 is taken for t = 1, which keeps the powers and the reciprocals defined; the update is then that of
+ *   a first step and is NOT the caller's intent -- the caller keeps its count consistent (Trainer: set_optimizer_steps, and
+ *   an assertion on the launch count).
+ *
+ * MBX_ERR_INVALID_ARG before any device work: n < 0, a null w, a null g (or m, v) with trainable != 0, mom given with momentum
+ * == 0 or missing otherwise, momentum or a beta outside [0, 1), eps <= 0, a negative wd_l2 or wd_decoupled, calls < 0, clipped
+ * != 0 without ctl; a NaN fails each of these.  n == 0: MBX_OK, nothing launched.
+ * Measured (tools/optimizer_bench.py, profiles/optimizer_bench.txt): bytes/s of each rule beside mbx_rmsprop_ema_step in the same
+ * graph replays.  What the rules do to AP or convergence on real data is not measured: no dataset or trained model is at hand.  */
+int mbx_sgd_ema_step(float* w, const float* g, float* mom /*NULL iff momentum==0*/, float* ema /*or NULL*/,
+                     void* w_bf16 /*or NULL*/, int64_t n, float lr, float momentum, int nesterov, float wd_l2, float ema_decay,
+                     int trainable, float* reg_loss, const float* ctl, int clipped, mbx_stream_t stream);
+int mbx_adam_ema_step(float* w, const float* g, float* m, float* v, float* ema /*or NULL*/, void* w_bf16 /*or NULL*/,
+                      int64_t n, float lr, float beta1, float beta2, float eps, float wd_l2, float wd_decoupled, int64_t calls,
+                      const int64_t* skipped /*DEVICE, or NULL*/, float ema_decay, int trainable, float* reg_loss,
+                      const float* ctl, int clipped, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ training input augmentation (row F1)
  * The pixel half of the reference's training input graph (inputs.py:264-351: crop, tf.image.resize_images with a
  * random ResizeMethod, distort_color, random_flip_left_right, (image - 0.5) * 2) for one batch.  The host draws every

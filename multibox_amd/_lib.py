@@ -107,6 +107,8 @@ _SIGS = {
     "mbx_grad_sqnorm": (I, [P, P, C.c_int64, F, P, P]),
     "mbx_clip_finalize": (I, [P, C.c_int64, D, P, P, P, P]),
     "mbx_rmsprop_ema_step_clipped": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, I, P, P, P]),
+    "mbx_sgd_ema_step": (I, [P, P, P, P, P, C.c_int64, F, F, I, F, F, I, P, P, I, P]),
+    "mbx_adam_ema_step": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, C.c_int64, P, F, I, P, P, I, P]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """Checkpoint / resume: the reference saves every variable with tf.train.Saver
 (train.py:282-286) and inference restores the EMA shadows into the live variables
 (detect.py:336-346).  Here: one .pt file `model.ckpt-<global_step>.pt` holding the flat
-buffers (weights, betas, moving statistics, RMSProp slots, EMA shadows, step) plus the
+buffers (weights, betas, moving statistics, the update rule and its slots, EMA shadows, step) plus the
 name index; TensorFlow V1 checkpoints are read by multibox_amd/tf_checkpoint.py into the same structure."""
 import glob
 import os
@@ -44,6 +44,9 @@ def _prune(logdir, max_to_keep, keep_every_n_hours, now=None):
     os.replace(tmp, state_path)
 
 
+SLOTS = ("Wms", "Btms", "Wmom", "Btmom")          # optimiser slots: a rule keeps some of them, the trainer holds None for the rest
+
+
 def save(logdir, trainer, max_to_keep=3, keep_checkpoint_every_n_hours=10000.0):
     net = trainer.net
     os.makedirs(logdir, exist_ok=True)
@@ -53,10 +56,13 @@ def save(logdir, trainer, max_to_keep=3, keep_checkpoint_every_n_hours=10000.0):
     state = dict(global_step=gstep, k=net.k, input_size=net.S,
                  index={n: (b, o, tuple(s), c) for n, (b, o, s, c) in net.param_index.items()},
                  W=net.W.cpu(), Bt=net.Bt.cpu(), MM=net.MM.cpu(), MV=net.MV.cpu(),
-                 Wms=trainer.Wms.cpu(), Btms=trainer.Btms.cpu(),
                  Wema=trainer.Wema.cpu(), Btema=trainer.Btema.cpu(), MMema=trainer.MMema.cpu(), MVema=trainer.MVema.cpu())
-    if trainer.Wmom is not None:                    # RMSPROP_MOMENTUM != 0: the momentum slots are optimiser state too
-        state.update(Wmom=trainer.Wmom.cpu(), Btmom=trainer.Btmom.cpu())
+    # the update rule and whichever of its slots exist (Wms: none under sgd; Wmom: none at momentum 0); opt_steps: the steps
+    # applied on these slots (Adam's bias correction counts them)
+    state.update(optimizer=trainer.optimizer, opt_steps=trainer.optimizer_steps() + gstep - trainer.global_step)
+    for name in SLOTS:
+        if getattr(trainer, name) is not None:
+            state[name] = getattr(trainer, name).cpu()
     tmp = path + ".tmp"                             # a kill in mid-save must not leave a truncated newest checkpoint
     torch.save(state, tmp)
     os.replace(tmp, path)
@@ -124,7 +130,9 @@ def restore_pretrained(path, trainer, fine_tune=False, use_moving_averages=False
             net.fold_bn()
     else:
         restore_for_training(ck, trainer)
-    trainer.global_step = 0
+    steps = trainer.optimizer_steps()               # (the slots keep their step count -- Adam's bias correction -- 0 under another
+    trainer.global_step = 0                         # rule than the checkpoint's; the schedule starts over either way)
+    trainer.set_optimizer_steps(steps)
     trainer.refresh_frozen_reg()
     return ck
 
@@ -135,12 +143,22 @@ def restore_for_training(path, trainer):
     assert st["W"].numel() == net.nW and st["k"] == net.k, "checkpoint does not match the network"
     for name, t in (("W", net.W), ("Bt", net.Bt), ("MM", net.MM), ("MV", net.MV)):
         t.copy_(st[name])
-    for name in ("Wms", "Btms", "Wema", "Btema", "MMema", "MVema"):
+    for name in ("Wema", "Btema", "MMema", "MVema"):
         getattr(trainer, name).copy_(st[name])
-    if trainer.Wmom is not None and "Wmom" in st:
-        trainer.Wmom.copy_(st["Wmom"])
-        trainer.Btmom.copy_(st["Btmom"])
     trainer.global_step = int(st["global_step"])
+    # The slots belong to the update rule (a checkpoint without the key is an rmsprop one).  Under another rule than the
+    # checkpoint's they mean something else: variables, shadows and global_step are restored, the slots keep their initial
+    # values, the optimiser starts counting its steps at 0 and the log gets an event.
+    was, now = st.get("optimizer", "rmsprop"), trainer.optimizer
+    if was == now:
+        for name in SLOTS:
+            if getattr(trainer, name) is not None and name in st:
+                getattr(trainer, name).copy_(st[name])
+        trainer.set_optimizer_steps(st.get("opt_steps", trainer.global_step))
+    else:
+        trainer.set_optimizer_steps(0)
+        trainer.events.append({"event": "optimizer_changed", "global_step": trainer.global_step, "checkpoint_optimizer": was,
+                               "optimizer": now})
     net.refresh_bf16()
     if net.fine_tune:
         net.fold_bn()

@@ -147,3 +147,81 @@ def grad_clip(cfg):
     if not (isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0):
         raise ValueError("CLIP_GRADIENT_NORM must be a number > 0 (.inf = guard only), got %r" % (v,))
     return float(v)
+
+
+OPTIMIZERS = ("rmsprop", "sgd", "adam", "adamw")
+_ADAM_KEYS = ("ADAM_BETA1", "ADAM_BETA2", "ADAM_EPSILON")
+# the keys each rule reads (the RMSPROP_* keys sit in DEFAULTS and are ignored under the other rules)
+OPTIMIZER_KEYS = {"rmsprop": (), "sgd": ("SGD_MOMENTUM", "SGD_NESTEROV"), "adam": _ADAM_KEYS, "adamw": _ADAM_KEYS + ("ADAMW_WEIGHT_DECAY",)}
+
+
+def check_optimizer_args(optimizer, sgd_momentum=0.9, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01):
+    """The ranges optimizer() holds the config keys to, on the Trainer's keyword arguments (whichever rule is chosen):
+    raises ValueError naming the argument."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if optimizer not in OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
+    for what, v in (("sgd_momentum", sgd_momentum), ("adam_beta1", adam_beta1), ("adam_beta2", adam_beta2)):
+        if not (number(v) and 0 <= v < 1):
+            raise ValueError("%s must be a number in [0, 1), got %r" % (what, v))
+    if not (number(adam_epsilon) and 0 < ctypes.c_float(adam_epsilon).value < float("inf")):
+        raise ValueError("adam_epsilon must be a finite number > 0 as a float32, got %r" % (adam_epsilon,))
+    if not (number(adamw_weight_decay) and 0 <= ctypes.c_float(adamw_weight_decay).value < float("inf")):
+        raise ValueError("adamw_weight_decay must be a finite number >= 0, got %r" % (adamw_weight_decay,))
+
+
+def optimizer(cfg):
+    """The update rule (mbx_sgd_ema_step / mbx_adam_ema_step; the reference has RMSProp alone, so off when absent) and the
+    learning-rate warm-up: a dict of Trainer keyword arguments, empty when neither key is set.
+      OPTIMIZER  absent, null or rmsprop: the reference's step under the RMSPROP_* keys.
+        sgd    tf.train.MomentumOptimizer on total_loss: SGD_MOMENTUM (a number in [0, 1), default 0.9), SGD_NESTEROV (a bool,
+               default false).
+        adam   Adam on total_loss, the L2 term in the gradient: ADAM_BETA1 (in [0, 1), default 0.9), ADAM_BETA2 (in [0, 1),
+               default 0.999), ADAM_EPSILON (finite and > 0 as a float32, default 1e-8).
+        adamw  the adam keys and ADAMW_WEIGHT_DECAY (finite and >= 0, default 0.01): decoupled decay of the trainable filters;
+               the coupled L2 term leaves the loss and the gradient.
+      LEARNING_RATE_WARMUP_STEPS  an int >= 0 (absent, null or 0 = off), with any rule: the learning rate of step t is the
+        schedule's times min(1, (t + 1) / warmup).
+    A key of another rule than the chosen one, a bool where a number is expected (or the reverse), a string, a list, a NaN
+    or a value out of range raises ValueError naming the key.  Host code only."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    kind = cfg.get("OPTIMIZER")
+    if kind is not None and not (isinstance(kind, str) and kind in OPTIMIZERS):
+        raise ValueError("OPTIMIZER must be one of %s, got %r" % (", ".join(OPTIMIZERS), kind))
+    own = OPTIMIZER_KEYS[kind or "rmsprop"]
+    for keys in OPTIMIZER_KEYS.values():
+        for key in keys:
+            if key not in own and cfg.get(key) is not None:
+                raise ValueError("%s does not go with OPTIMIZER %s" % (key, kind or "rmsprop (the default)"))
+    out = {}
+    if kind is not None:
+        out["optimizer"] = kind
+
+    def unit(key, default):                                   # a number in [0, 1)
+        v = cfg.get(key)
+        if v is None:
+            return default
+        if not (number(v) and 0 <= v < 1):
+            raise ValueError("%s must be a number in [0, 1), got %r" % (key, v))
+        return float(v)
+    if kind == "sgd":
+        nesterov = cfg.get("SGD_NESTEROV")
+        if nesterov is not None and not isinstance(nesterov, bool):
+            raise ValueError("SGD_NESTEROV must be true or false, got %r" % (nesterov,))
+        out.update(sgd_momentum=unit("SGD_MOMENTUM", 0.9), sgd_nesterov=bool(nesterov))
+    elif kind in ("adam", "adamw"):
+        eps = cfg.get("ADAM_EPSILON")
+        if eps is not None and not (number(eps) and 0 < ctypes.c_float(eps).value < float("inf")):
+            raise ValueError("ADAM_EPSILON must be a finite number > 0 as a float32, got %r" % (eps,))
+        out.update(adam_beta1=unit("ADAM_BETA1", 0.9), adam_beta2=unit("ADAM_BETA2", 0.999),
+                   adam_epsilon=1e-8 if eps is None else float(eps))
+        if kind == "adamw":
+            wd = cfg.get("ADAMW_WEIGHT_DECAY")
+            if wd is not None and not (number(wd) and 0 <= ctypes.c_float(wd).value < float("inf")):
+                raise ValueError("ADAMW_WEIGHT_DECAY must be a finite number >= 0, got %r" % (wd,))
+            out["adamw_weight_decay"] = 0.01 if wd is None else float(wd)
+    if cfg.get("LEARNING_RATE_WARMUP_STEPS") is not None:
+        warmup = _int_key(cfg, "LEARNING_RATE_WARMUP_STEPS", 0)
+        if warmup:
+            out["lr_warmup_steps"] = warmup
+    return out

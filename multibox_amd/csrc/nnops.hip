@@ -623,6 +623,154 @@ clip_finalize_kernel(const double* __restrict__ partials, long long n_slots, dou
 
 inline int sqnorm_grid(long long n) { return grid_for((n + 3) / 4); }
 
+// ------------------------------------------------------------------- optimiser choice (OPTIMIZER: sgd, adam, adamw)
+// The update rules beside RMSProp.  A rule is a host-side struct of hyper-parameters with kSlots (how many per-element slots it
+// keeps) and ready(), which runs once per thread and returns the element functor: new w = f(w, g', slot a, slot b).  Every
+// rounding of a functor is spelled out (fmaf, or a product / quotient / sum that stands alone: there is no a * b + c left for the
+// compiler to contract), so the clipped and unclipped instantiations and the vector and tail paths give the same bits.
+template <bool kMom>
+struct SgdRule {                                             // tf.train.MomentumOptimizer; kMom = false: momentum 0, no slot
+  static constexpr int kSlots = kMom ? 1 : 0;
+  float lr, momentum;
+  int nesterov;
+  __device__ __forceinline__ SgdRule ready() const { return *this; }
+  __device__ __forceinline__ float operator()(float w, float g, float& acc, float&) const {
+    if constexpr (!kMom) {
+      return fmaf(-lr, g, w);                                // w -= lr * g'
+    } else {
+      acc = fmaf(momentum, acc, g);                          // acc = momentum * acc + g'
+      return fmaf(-lr, nesterov ? fmaf(momentum, acc, g) : acc, w);    // w -= lr * acc, or lr * (g' + momentum * acc)
+    }
+  }
+};
+
+// b^t for an integer t >= 0 by squaring, in double (at most 63 rounds, lane-uniform)
+__device__ __forceinline__ double pow_int(double b, long long t) {
+  double r = 1.0;
+  for (; t > 0; t >>= 1, b *= b)
+    if (t & 1) r *= b;
+  return r;
+}
+
+struct AdamRule {                                            // Adam; wd_decoupled != 0: AdamW
+  static constexpr int kSlots = 2;
+  float lr, beta1, beta2, eps, wd_decoupled;
+  long long calls;
+  const long long* skipped;
+  struct Ready {
+    float lr, b1, omb1, b2, omb2, eps, wdd, c1, c2;
+    __device__ __forceinline__ float operator()(float w, float g, float& m, float& v) const {
+      m = fmaf(b1, m, omb1 * g);                             // m = beta1 * m + (1 - beta1) * g'
+      v = fmaf(b2, v, (omb2 * g) * g);                       // v = beta2 * v + (1 - beta2) * g'^2
+      const float mhat = m * c1, vhat = v * c2;              // m / bc1, v / bc2
+      const float denom = sqrtf(vhat) + eps;
+      float upd = mhat / denom;
+      if (wdd != 0.f) upd = fmaf(wdd, w, upd);               // + wd_decoupled * w, the weight before the step
+      return fmaf(-lr, upd, w);
+    }
+  };
+  // The bias corrections 1 / (1 - beta^t), t = the APPLIED steps including this one: the host's launch count less the steps the
+  // device skipped (read before this step's own increment, which comes later on the stream).  Once per thread, in double.
+  __device__ __forceinline__ Ready ready() const {
+    long long t = calls + 1 - (skipped ? *skipped : 0);
+    if (t < 1) t = 1;                                        // calls < *skipped breaks the contract (include/mbx.h): stay defined
+    const double bc1 = 1.0 - pow_int((double)beta1, t), bc2 = 1.0 - pow_int((double)beta2, t);
+    return Ready{lr, beta1, 1.0f - beta1, beta2, 1.0f - beta2, eps, wd_decoupled, (float)(1.0 / bc1), (float)(1.0 / bc2)};
+  }
+};
+
+// rmsprop_ema_kernel's surroundings around a rule: the gate, the EMA from the weight before the step, the regulariser sum, frozen
+// ranges, the bf16 refresh, 16-byte accesses where every stream in use is 16-byte aligned (wb 8-byte) and element by element
+// otherwise and for the n % 4 tail.  s0 / s1: the rule's slots (those beyond Rule::kSlots are never touched and may be NULL).
+// kClip: ctl is the clip block and g' = clip[2] * g'.  A pure streaming pass: no LDS beyond the regulariser's four partial sums.
+template <bool kClip, class Rule>
+__global__ void __launch_bounds__(kT)
+opt_ema_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+               float* __restrict__ ema, unsigned short* __restrict__ wb, long long n, float wd, float ema_decay, int trainable,
+               float* __restrict__ reg_loss, const float* __restrict__ ctl, const Rule rule) {
+  if (ctl && (ctl[0] != 0.f || ctl[1] != 0.f)) return;       // as rmsprop_ema_kernel
+  constexpr bool kA = Rule::kSlots >= 1, kB = Rule::kSlots >= 2;
+  float sq = 0.f;
+  float scale = 1.f;
+  if constexpr (kClip) scale = ctl[2];
+  const auto step = rule.ready();
+  auto one = [&](float wi, const float gi_, float& ai, float& bi, float& emai) -> float {
+    sq = fmaf(wi, wi, sq);
+    if (ema) emai = fmaf(-(1.0f - ema_decay), emai - wi, emai);       // emai - (1 - ema_decay) * (emai - wi)
+    if (trainable) {
+      float gi = opt_grad(gi_, wd, wi);
+      if constexpr (kClip) gi = scale * gi;
+      wi = step(wi, gi, ai, bi);
+    }
+    return wi;
+  };
+  const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | (kA ? reinterpret_cast<uintptr_t>(s0) : 0) |
+                     (kB ? reinterpret_cast<uintptr_t>(s1) : 0) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(wb) & 7) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n4; i += (long long)gridDim.x * kT) {
+    float4 wv = reinterpret_cast<const float4*>(w)[i];
+    float4 ev = ema ? reinterpret_cast<const float4*>(ema)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), av = gv, bv = gv;
+    if (trainable) {
+      gv = reinterpret_cast<const float4*>(g)[i];
+      if constexpr (kA) av = reinterpret_cast<const float4*>(s0)[i];
+      if constexpr (kB) bv = reinterpret_cast<const float4*>(s1)[i];
+    }
+    wv.x = one(wv.x, gv.x, av.x, bv.x, ev.x); wv.y = one(wv.y, gv.y, av.y, bv.y, ev.y);
+    wv.z = one(wv.z, gv.z, av.z, bv.z, ev.z); wv.w = one(wv.w, gv.w, av.w, bv.w, ev.w);
+    if (ema) reinterpret_cast<float4*>(ema)[i] = ev;
+    if (trainable) {
+      if constexpr (kA) reinterpret_cast<float4*>(s0)[i] = av;
+      if constexpr (kB) reinterpret_cast<float4*>(s1)[i] = bv;
+      reinterpret_cast<float4*>(w)[i] = wv;
+    }
+    if (wb) reinterpret_cast<uint2*>(wb)[i] = make_uint2(pack2bf(wv.x, wv.y), pack2bf(wv.z, wv.w));
+  }
+  for (long long i = 4 * n4 + (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
+    float ai = 0.f, bi = 0.f, emai = ema ? ema[i] : 0.f;
+    if (trainable) {
+      if constexpr (kA) ai = s0[i];
+      if constexpr (kB) bi = s1[i];
+    }
+    const float wi = one(w[i], trainable ? g[i] : 0.f, ai, bi, emai);
+    if (ema) ema[i] = emai;
+    if (trainable) {
+      if constexpr (kA) s0[i] = ai;
+      if constexpr (kB) s1[i] = bi;
+      w[i] = wi;
+    }
+    if (wb) wb[i] = (unsigned short)f2bf(wi);
+  }
+  if (reg_loss && wd != 0.f) {
+    sq = wave_sum(sq);
+    __shared__ float red[kT / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = 0.f;
+      for (int i = 0; i < kT / 64; ++i) t += red[i];
+      atomicAdd(reg_loss, 0.5f * wd * t);
+    }
+  }
+}
+
+template <class Rule>
+int launch_opt(int clipped, float* w, const float* g, float* s0, float* s1, float* ema, void* w_bf16, long long n, float wd,
+               float ema_decay, int trainable, float* reg_loss, const float* ctl, const Rule& rule, mbx_stream_t stream) {
+  MBX_ENTER();
+  if (clipped)
+    hipLaunchKernelGGL((opt_ema_kernel<true, Rule>), dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, s0, s1, ema, (us)w_bf16, n, wd,
+                       ema_decay, trainable, reg_loss, ctl, rule);
+  else
+    hipLaunchKernelGGL((opt_ema_kernel<false, Rule>), dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, s0, s1, ema, (us)w_bf16, n, wd,
+                       ema_decay, trainable, reg_loss, ctl, rule);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+inline bool in_unit(float b) { return b >= 0.f && b < 1.f; }       // [0, 1); false for a NaN
+
 }  // namespace
 
 // ================================================================================== C ABI
@@ -837,6 +985,32 @@ extern "C" int mbx_clip_finalize(const double* partials, int64_t n_slots, double
                      reinterpret_cast<long long*>(counts));
   MBX_LAUNCH_CHECK();
   return MBX_OK;
+}
+
+extern "C" int mbx_sgd_ema_step(float* w, const float* g, float* mom, float* ema, void* w_bf16, int64_t n, float lr, float momentum,
+                                int nesterov, float wd_l2, float ema_decay, int trainable, float* reg_loss, const float* ctl,
+                                int clipped, mbx_stream_t stream) {
+  if (!w || n < 0 || (trainable && !g) || !in_unit(momentum) || (mom != nullptr) != (momentum != 0.f) || !(wd_l2 >= 0.f) ||
+      (clipped && !ctl))
+    return MBX_ERR_INVALID_ARG;
+  if (n == 0) return MBX_OK;
+  if (mom)
+    return launch_opt(clipped, w, g, mom, nullptr, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
+                      SgdRule<true>{lr, momentum, nesterov}, stream);
+  return launch_opt(clipped, w, g, nullptr, nullptr, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
+                    SgdRule<false>{lr, 0.f, 0}, stream);
+}
+
+extern "C" int mbx_adam_ema_step(float* w, const float* g, float* m, float* v, float* ema, void* w_bf16, int64_t n, float lr,
+                                 float beta1, float beta2, float eps, float wd_l2, float wd_decoupled, int64_t calls,
+                                 const int64_t* skipped, float ema_decay, int trainable, float* reg_loss, const float* ctl,
+                                 int clipped, mbx_stream_t stream) {
+  if (!w || n < 0 || (trainable && (!g || !m || !v)) || !in_unit(beta1) || !in_unit(beta2) || !(eps > 0.f) || !(wd_l2 >= 0.f) ||
+      !(wd_decoupled >= 0.f) || calls < 0 || (clipped && !ctl))
+    return MBX_ERR_INVALID_ARG;
+  if (n == 0) return MBX_OK;
+  return launch_opt(clipped, w, g, m, v, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
+                    AdamRule{lr, beta1, beta2, eps, wd_decoupled, (long long)calls, reinterpret_cast<const long long*>(skipped)}, stream);
 }
 
 extern "C" int mbx_ema_update(float* ema, const float* value, int64_t n, float ema_decay, const float* skip_ctl,

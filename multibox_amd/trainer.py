@@ -18,6 +18,7 @@ import re
 import torch
 
 from . import _lib
+from .config import check_optimizer_args
 from .engine import Net, WEIGHT_DECAY
 from .loss import MultiboxLoss
 from .dist import BucketReducer
@@ -36,13 +37,20 @@ def learning_rate(step, lr0, dsteps, factor, staircase=True):
     return float(lr0) * float(factor) ** p
 
 
+def warmup_factor(step, warmup_steps):
+    """LEARNING_RATE_WARMUP_STEPS: what the trainer multiplies learning_rate() by at `step` -- min(1, (step + 1) / warmup);
+    1 when the warm-up is off (0 or None)."""
+    return min(1.0, (step + 1.0) / warmup_steps) if warmup_steps else 1.0
+
+
 class Trainer:
     def __init__(self, net: Net, bbox_priors, max_num_bboxes=13, location_loss_alpha=1000.0, initial_learning_rate=0.01,
                  decay_steps_=7116, learning_rate_decay_factor=0.94, staircase=True, rmsprop_decay=0.9,
                  rmsprop_momentum=0.0, rmsprop_epsilon=1.0, moving_average_decay=0.9999, use_graph=True,
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
                  match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
-                 clip_gradient_norm=None):
+                 clip_gradient_norm=None, optimizer="rmsprop", sgd_momentum=0.9, sgd_nesterov=False, adam_beta1=0.9,
+                 adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0):
         assert net.mode == "train"
         self.net = net
         self.pg = process_group
@@ -63,10 +71,29 @@ class Trainer:
         # trainable ranges of the flat buffers (heads are last in forward order)
         self.w_lo = net.head_w_start if net.fine_tune else 0
         self.bt_lo = net.head_bt_start if net.fine_tune else 0
-        self.Wms = torch.ones(net.nW, **f32)            # TF initialises the rms slot to ones
-        self.Btms = torch.ones(net.nBt, **f32)
-        self.Wmom = torch.zeros(net.nW, **f32) if self.momentum != 0.0 else None
-        self.Btmom = torch.zeros(net.nBt, **f32) if self.momentum != 0.0 else None
+        # optimizer: the update rule (None = rmsprop, the reference's).  sgd: tf.train.MomentumOptimizer; adam: Adam, the L2
+        # term in the gradient as under rmsprop; adamw: Adam with adamw_weight_decay as a DECOUPLED decay of the trainable
+        # filters (betas: none) -- the coupled L2 term then leaves the loss and the gradient: wd_l2, the coefficient of the
+        # optimiser launch, of the clipped norm, of reg_loss and of frozen_reg, is 0.  lr_warmup_steps: warmup_factor().
+        self.optimizer = optimizer or "rmsprop"
+        # (for callers that build a Trainer themselves: a bad value is named here, not by the library's argument error at
+        # the first launch)
+        check_optimizer_args(self.optimizer, sgd_momentum, adam_beta1, adam_beta2, adam_epsilon, adamw_weight_decay)
+        self.sgd_momentum, self.sgd_nesterov = float(sgd_momentum), bool(sgd_nesterov)
+        self.adam_beta1, self.adam_beta2, self.adam_eps = float(adam_beta1), float(adam_beta2), float(adam_epsilon)
+        self.wd_decoupled = float(adamw_weight_decay) if self.optimizer == "adamw" else 0.0
+        self.wd_l2 = 0.0 if self.optimizer == "adamw" else WEIGHT_DECAY
+        self.warmup_steps = int(lr_warmup_steps or 0)
+        # applied optimiser steps less global_step: 0 unless a restore moved one without the other (set_optimizer_steps)
+        self._opt_step_offset = 0
+        # slots.  Wmom / Btmom: RMSProp's and SGD's momentum accumulator (None at momentum 0) or Adam's first moment;
+        # Wms / Btms: RMSProp's mean square (TF initialises it to ones) or Adam's second moment (zeros); None under sgd
+        has_mom = {"rmsprop": self.momentum != 0.0, "sgd": self.sgd_momentum != 0.0}.get(self.optimizer, True)
+        second = None if self.optimizer == "sgd" else torch.ones if self.optimizer == "rmsprop" else torch.zeros
+        self.Wms = second(net.nW, **f32) if second else None
+        self.Btms = second(net.nBt, **f32) if second else None
+        self.Wmom = torch.zeros(net.nW, **f32) if has_mom else None
+        self.Btmom = torch.zeros(net.nBt, **f32) if has_mom else None
         # EMA shadows of every model variable, incl. BN moving statistics (train.py:257)
         self.Wema, self.Btema = net.W.clone(), net.Bt.clone()
         self.MMema, self.MVema = net.MM.clone(), net.MV.clone()
@@ -147,8 +174,8 @@ class Trainer:
         """Regulariser of the frozen backbone under --fine_tune: a constant that train.py:246 still adds to the total
         loss.  Recomputed after every restore (the weights it is taken from change there)."""
         self.frozen_reg = 0.0
-        if self.w_lo > 0:
-            self.frozen_reg = float(0.5 * WEIGHT_DECAY * (self.net.W[:self.w_lo].double() ** 2).sum())
+        if self.w_lo > 0 and self.wd_l2:
+            self.frozen_reg = float(0.5 * self.wd_l2 * (self.net.W[:self.w_lo].double() ** 2).sum())
 
     def _optimizer_ranges(self, scopes):
         """[(buffer 'W' | 'Bt', lo, hi, trainable)] covering the trainable part of both flat buffers, adjacent ranges of
@@ -200,9 +227,10 @@ class Trainer:
                   self.MMema, self.MVema):
             if t is not None:
                 dist.broadcast(t, src=src, group=self.pg)
-        step = torch.tensor([self.global_step], dtype=torch.int64, device=net.W.device)
+        # (getattr, as for skipped_steps in fold_skipped: a trainer assembled without __init__ broadcasts too)
+        step = torch.tensor([self.global_step, getattr(self, "_opt_step_offset", 0)], dtype=torch.int64, device=net.W.device)
         dist.broadcast(step, src=src, group=self.pg)
-        self.global_step = int(step)
+        self.global_step, self._opt_step_offset = (int(v) for v in step.tolist())
         if net.W.is_cuda:
             net.refresh_bf16()
             if net.fine_tune:
@@ -544,29 +572,59 @@ class Trainer:
         for i in range(len(self._segments)):
             self._run_segment(i)
 
-    def _optimizer(self):
+    def set_optimizer_steps(self, k):
+        """The optimiser has applied k steps on its present slots (Adam's bias correction counts them): a restore calls
+        this when it moves global_step and the slots apart (another rule's checkpoint: 0)."""
+        self._opt_step_offset = int(k) - self.global_step
+
+    def optimizer_steps(self):
+        """Steps the optimiser has applied on its present slots, as of the last fold of skipped steps."""
+        return self.global_step + self._opt_step_offset
+
+    def _range_step(self, buf, lo, hi, on, lr, d, gate, clipped, s):
+        """The optimiser launch of one range of self.opt_ranges under the chosen rule.  gate: the step control block, or the
+        clip block with clipped = True.  Filters carry the L2 coefficient, the regulariser sum, the bf16 refresh and (adamw)
+        the decoupled decay; betas none of them."""
         net, l = self.net, _lib.lib()
+        n = hi - lo
+        if n <= 0:
+            return
+        P = lambda t_, el=4: None if t_ is None else t_.data_ptr() + el * lo
+        filt = buf == "W"
+        w, g, ms, mom, ema = (net.W, net.Wg, self.Wms, self.Wmom, self.Wema) if filt else (net.Bt, net.Btg, self.Btms, self.Btmom, self.Btema)
+        wb, wd, reg = (P(net.Wb, 2), self.wd_l2, net.reg_loss.data_ptr()) if filt else (None, 0.0, None)
+        what = "%s %s%s" % (self.optimizer, "W" if filt else "beta", " (clipped)" if clipped else "")
+        if self.optimizer == "rmsprop":
+            entry = l.mbx_rmsprop_ema_step_clipped if clipped else l.mbx_rmsprop_ema_step
+            st = entry(P(w), P(g), P(ms), P(mom), P(ema), wb, n, lr, self.rms_decay, self.momentum, self.eps, wd, d, on, reg, gate, s)
+        elif self.optimizer == "sgd":
+            st = l.mbx_sgd_ema_step(P(w), P(g), P(mom), P(ema), wb, n, lr, self.sgd_momentum, int(self.sgd_nesterov), wd, d, on, reg,
+                                    gate, int(clipped), s)
+        else:
+            # launches so far on these slots, skipped ones included: the kernel takes the device's count of those off again
+            # (never below the device's count of skipped steps: every skip was a launch, and both restores set the offset)
+            calls = self.global_step + self._opt_step_offset + self._skipped_seen
+            assert calls >= 0, "optimizer step count out of step with global_step (%d, offset %d)" % (self.global_step, self._opt_step_offset)
+            st = l.mbx_adam_ema_step(P(w), P(g), P(mom), P(ms), P(ema), wb, n, lr, self.adam_beta1, self.adam_beta2, self.adam_eps, wd,
+                                     self.wd_decoupled if filt else 0.0, calls, self.skipped_steps.data_ptr(), d, on, reg, gate,
+                                     int(clipped), s)
+        _lib.check(st, what)
+
+    def _optimizer(self):
+        net = self.net
         s = torch.cuda.current_stream().cuda_stream
         t = self.global_step
         lr = learning_rate(t, self.lr0, self.dsteps, self.lr_factor, self.staircase)
+        if self.warmup_steps:
+            lr *= warmup_factor(t, self.warmup_steps)
         d = min(self.ema_decay, (1.0 + t) / (10.0 + t))        # ExponentialMovingAverage(num_updates=global_step)
         self.lr = lr
         # (net.reg_loss was cleared by the step's mbx_step_begin launch: Net.zero_grads)
-        P = lambda t_, off=0: None if t_ is None else t_.data_ptr() + 4 * off
         ctl = net.step_ctl.data_ptr()                  # non-zero -> every launch below is a no-op (poisoned step / stop request)
         if self.clip_norm is not None:
             return self._optimizer_clipped(lr, d, s)
         for buf, lo, hi, on in self.opt_ranges:
-            n = hi - lo
-            if n <= 0:
-                continue
-            if buf == "W":
-                _lib.check(l.mbx_rmsprop_ema_step(P(net.W, lo), P(net.Wg, lo), P(self.Wms, lo), P(self.Wmom, lo), P(self.Wema, lo),
-                                                  net.Wb.data_ptr() + 2 * lo, n, lr, self.rms_decay, self.momentum, self.eps,
-                                                  WEIGHT_DECAY, d, on, net.reg_loss.data_ptr(), ctl, s), "rmsprop W")
-            else:
-                _lib.check(l.mbx_rmsprop_ema_step(P(net.Bt, lo), P(net.Btg, lo), P(self.Btms, lo), P(self.Btmom, lo), P(self.Btema, lo),
-                                                  None, n, lr, self.rms_decay, self.momentum, self.eps, 0.0, d, on, None, ctl, s), "rmsprop beta")
+            self._range_step(buf, lo, hi, on, lr, d, ctl, False, s)
         # moving statistics <- this step's batch statistics, and their EMA shadows (train.py:257) from the new values: one gated launch
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
         net.apply_moving_update(net.step_ctl, self.skipped_steps, self.MMema, self.MVema, d)
@@ -584,26 +642,15 @@ class Trainer:
             if not k:
                 continue
             part = self._clip_partials.data_ptr() + 8 * slot
-            if buf == "W":
-                _lib.check(l.mbx_grad_sqnorm(P(net.Wg, lo), P(net.W, lo), hi - lo, WEIGHT_DECAY, part, s), "grad_sqnorm W")
+            if buf == "W":                             # (adamw: no coupled L2 term, the norm is that of g alone)
+                _lib.check(l.mbx_grad_sqnorm(P(net.Wg, lo), P(net.W, lo) if self.wd_l2 else None, hi - lo, self.wd_l2, part, s), "grad_sqnorm W")
             else:
                 _lib.check(l.mbx_grad_sqnorm(P(net.Btg, lo), None, hi - lo, 0.0, part, s), "grad_sqnorm beta")
             slot += k
         _lib.check(l.mbx_clip_finalize(self._clip_partials.data_ptr(), max(1, slot), self.clip_norm, net.step_ctl.data_ptr(),
                                        self._clip_block.data_ptr(), self._clip_counts.data_ptr(), s), "clip_finalize")
-        clip = self._clip_block.data_ptr()
         for buf, lo, hi, on in self.opt_ranges:
-            n = hi - lo
-            if n <= 0:
-                continue
-            if buf == "W":
-                _lib.check(l.mbx_rmsprop_ema_step_clipped(P(net.W, lo), P(net.Wg, lo), P(self.Wms, lo), P(self.Wmom, lo), P(self.Wema, lo),
-                                                          net.Wb.data_ptr() + 2 * lo, n, lr, self.rms_decay, self.momentum, self.eps,
-                                                          WEIGHT_DECAY, d, on, net.reg_loss.data_ptr(), clip, s), "rmsprop W (clipped)")
-            else:
-                _lib.check(l.mbx_rmsprop_ema_step_clipped(P(net.Bt, lo), P(net.Btg, lo), P(self.Btms, lo), P(self.Btmom, lo), P(self.Btema, lo),
-                                                          None, n, lr, self.rms_decay, self.momentum, self.eps, 0.0, d, on, None, clip, s),
-                           "rmsprop beta (clipped)")
+            self._range_step(buf, lo, hi, on, lr, d, self._clip_block.data_ptr(), True, s)
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
         net.apply_moving_update(self._clip_block, self.skipped_steps, self.MMema, self.MVema, d)
         net.prepare_filters()

@@ -48,7 +48,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, grad_clip
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, grad_clip, optimizer
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -76,6 +76,7 @@ def main():
         focal = focal_loss(cfg)                   # [new] LOSS_FOCAL_GAMMA / LOSS_FOCAL_ALPHA: focal loss, off when absent
         loc_term = loc_loss(cfg)                  # [new] LOSS_LOC_TYPE / LOSS_LOC_BETA: the location term, L2 when absent
         clip_norm = grad_clip(cfg)                # [new] CLIP_GRADIENT_NORM: global-norm clipping + non-finite guard, off when absent
+        opt = optimizer(cfg)                      # [new] OPTIMIZER (+ its keys) / LEARNING_RATE_WARMUP_STEPS: RMSProp, no warm-up when absent
     except ValueError as e:
         raise SystemExit("config: %s" % e)
     torch.cuda.set_device(local_rank)
@@ -100,7 +101,7 @@ def main():
                  neg_per_pos=mining[0] if mining else None, min_neg=mining[1] if mining else 0,
                  match_iou_threshold=match_iou, focal_gamma=focal[0] if focal else None,
                  focal_alpha=focal[1] if focal else None, loc_loss=loc_term[0] if loc_term else None,
-                 loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm)
+                 loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm, **opt)
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -197,6 +198,10 @@ def main():
             if clip_norm is not None:
                 rec.update(grad_norm=tr.grad_norm(), clip_scale=tr.clip_scale(), clipped_steps=tr.clipped_steps(),
                            nonfinite_steps=tr.nonfinite_steps())
+            if "optimizer" in opt:
+                rec["optimizer"] = opt["optimizer"]
+            if "lr_warmup_steps" in opt:
+                rec["warmup_steps"] = opt["lr_warmup_steps"]
             print("global step %d: loss = %.4f (loc %.4f conf %.4f) lr %.6f %.1f img/s" % (tr.global_step, total, loc, conf, tr.lr, ips))
             log.write(json.dumps(rec) + "\n")
             log.flush()

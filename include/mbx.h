@@ -112,6 +112,55 @@ int mbx_match_extend(const float* priors /*[P,4] x1,y1,x2,y2*/, const float* gt 
                      int32_t* match /*[B,P] IN/OUT: mbx_match's output*/,
                      int32_t* n_extra /*[B] or NULL*/, mbx_stream_t stream);
 
+/* ATSS MATCHING behind mbx_match (Adaptive Training Sample Selection, Zhang et al., CVPR 2020; optional, not in the
+ * reference, off unless the caller asks; the alternative to mbx_match_extend -- a caller runs one of the two).  Instead of
+ * one hand-picked IoU number every box gets a threshold of its own from the priors around it.  `priors` are the priors as
+ * corners, `match` is mbx_match's output and is updated in place, as for mbx_match_extend.  The priors are described in
+ * pyramid LEVELS: level_start[0 .. n_levels], a HOST array read at the call and handed to the kernel by value, with
+ * level_start[0] = 0, strictly ascending, level_start[n_levels] = P; level l holds priors [level_start[l], level_start[l+1]).
+ * All arithmetic is float64 on the float32 inputs widened to double, in exactly this order, no product fused into a sum.
+ * Per image b, with n = n_gt[b]:
+ *   status[b] != 0, n <= 0 or n > G: the image is SKIPPED, its row of `match` stays byte for byte as it was,
+ *   n_extra[b] = 0 and thr[b, :] = 0.0 (mbx_match_extend's skip rule).
+ *   Centres, of priors and boxes alike:  cx = (x1 + x2) * 0.5,  cy = (y1 + y2) * 0.5.
+ *   Distance of box j < n and prior p:  dx = cx_p - cx_j,  dy = cy_p - cy_j,  d2 = dx * dx + dy * dy.
+ *   CANDIDATES of box j: on every level the min(topk, level size) priors with the smallest d2; equal d2 goes to the lowest
+ *   prior index; a NaN d2 ranks behind every number, +inf included, by index among NaNs.  m = sum over the levels of
+ *   min(topk, size_l) is the same for every box of a call.
+ *   IoU of a candidate: mbx_match_extend's, term by term, the prior first.
+ *   THRESHOLD of box j, over its m candidate IoUs taken in ascending prior index, each sum starting from 0.0:
+ *     mean = (sum iou) / m;   var = (sum (iou - mean) * (iou - mean)) / (m - 1);   std = sqrt(var), 0.0 when m == 1;
+ *     thr_j = mean + std
+ *   (the sample standard deviation, as in the authors' code).  Every candidate counts: those mbx_match assigned and those
+ *   with IoU 0 too.
+ *   A candidate p is a POSITIVE of j iff  iou > 0  and  iou >= thr_j (not strict; a NaN fails it)  and the prior's centre is
+ *   strictly inside the box:  x1_j < cx_p && cx_p < x2_j && y1_j < cy_p && cy_p < y2_j.
+ *   ASSIGNMENT: every prior with match[b,p] < 0 that is a positive of at least one box gets the box of the largest IoU, the
+ *   lowest j among equals.  A prior that mbx_match assigned keeps its box.  Rows j >= n of `gt` are never read.
+ *   n_extra[b] = the number of priors newly assigned;  thr[b,j] = thr_j for j < n and 0.0 for j >= n.  Each may be NULL;
+ *   every element is written on every call (no memset by the caller).
+ * An image's row depends on its own inputs only -- not on B or its place in the launch -- and the same input gives the same
+ * bytes on every call: no floating-point atomics; the claims are resolved by an unsigned 64-bit max on IoU bit patterns in
+ * LDS and an unsigned integer min on `match`, neither of which depends on the order of arrival.
+ * With k priors per cell sharing one centre, topk = 9 reaches about 9 / k cells of a level (about two at k = 5): a caller who
+ * wants the paper's nine LOCATIONS passes 9 * k.
+ * NULL priors / level_start / gt / n_gt / status / match, B < 0, P <= 0, G <= 0, topk < 1, n_levels outside [1, 8] or a
+ * level_start that does not start at 0, is not strictly ascending or does not end at P: MBX_ERR_INVALID_ARG.  The launch
+ * holds an image in the LDS of a plain launch:
+ *     8 P + 40 G + 2 G m + 8 W m + 128  <=  65536 bytes,   W = the most of 16, 8, 4, 2, 1 wavefronts that fits,  and P < 65535;
+ * a size with no such W: MBX_ERR_UNSUPPORTED.  (P = 4221, G = 100, six levels, topk = 9 -- m <= 54 -- needs 54 KB at W = 16;
+ * P = 646, G = 13 fits at every topk.)  Nothing is launched or written for either error.  B == 0: MBX_OK.
+ * mbx_match_atss_supported gives the same verdict for a size, on a host without a GPU too.  No environment variable is read.
+ * One launch on `stream`, one workgroup per image, no workspace, graph-capturable (level_start is not read after the call
+ * returns).  The four loss entries read the extended `match` as they read any other; mining counts its positives from it.
+ * What ATSS does to AP on real data is NOT measured here: no trained model or dataset is at hand.                         */
+int mbx_match_atss_supported(int P, int G, int n_levels, const int32_t* level_start /*HOST [n_levels+1]*/, int topk);
+int mbx_match_atss(const float* priors /*[P,4] x1,y1,x2,y2*/, const int32_t* level_start /*HOST [n_levels+1]*/,
+                   int n_levels, const float* gt /*[B,G,4]*/, const int32_t* n_gt /*[B]*/,
+                   const int32_t* status /*[B], as mbx_match left it*/, int topk, int B, int P, int G,
+                   int32_t* match /*[B,P] IN/OUT: mbx_match's output*/, int32_t* n_extra /*[B] or NULL*/,
+                   double* thr /*[B,G] or NULL*/, mbx_stream_t stream);
+
 /* ---------------------------------------------------------------- loss fwd+bwd (A7)
  * loss.py:88-101 given the matching: loc_loss = alpha * 1/2 sum (decoded-gt)^2 over
  * matched rows; conf_loss = -sum log(c_matched) - sum log(1 - c_unmatched + 1e-10),

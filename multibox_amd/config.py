@@ -86,6 +86,22 @@ def match_iou_threshold(cfg):
     return float(v)
 
 
+def atss_matching(cfg):
+    """ATSS matching behind the bipartite match (mbx_match_atss; not in the reference, so off when absent): None, or
+    LOSS_MATCH_ATSS_TOPK as an int >= 1 (absent or null = off).  Per box the key's number of priors nearest to its centre on
+    every pyramid level are candidates, and the free ones at or over the mean plus the standard deviation of the
+    candidates' IoUs, with their centre in the box, become its positives.  With NUM_BBOXES_PER_CELL priors sharing a centre,
+    9 reaches about two cells of a level; the paper's nine locations are 9 * NUM_BBOXES_PER_CELL.  Not together with
+    LOSS_MATCH_IOU_THRESHOLD (both decide what a free prior becomes): ValueError naming both keys.  A bool, a float with a
+    fraction, a string, a list, a NaN or a value < 1 raises ValueError naming the key.  Host code only."""
+    if cfg.get("LOSS_MATCH_ATSS_TOPK") is None:
+        return None
+    topk = _int_key(cfg, "LOSS_MATCH_ATSS_TOPK", 1)
+    if cfg.get("LOSS_MATCH_IOU_THRESHOLD") is not None:
+        raise ValueError("LOSS_MATCH_ATSS_TOPK and LOSS_MATCH_IOU_THRESHOLD are both given: choose one matching rule")
+    return topk
+
+
 def focal_loss(cfg):
     """Focal loss on the confidence term (mbx_loss_fwd_bwd_focal; not in the reference, so off when absent): None, or
     (gamma, alpha_or_None) from LOSS_FOCAL_GAMMA (a number in [0, 10]; absent or null = off) and LOSS_FOCAL_ALPHA (a number

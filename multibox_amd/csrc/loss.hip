@@ -1,4 +1,4 @@
-// libmbx: the training side of the box arithmetic -- prior decode, bipartite matching, threshold matching, loss fwd+bwd
+// libmbx: the training side of the box arithmetic -- prior decode, bipartite matching, threshold / ATSS matching, loss fwd+bwd
 // (plain, with hard-negative mining, focal, with a choice of location term).  The detection side is postproc.hip.
 // HBM/latency-bound integer+float kernels; one workgroup per image,
 // wave64 shuffle reductions.  Built with -ffp-contract=off: the float32 cost arithmetic
@@ -259,6 +259,265 @@ match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict_
   if (tid == 0) {
     int total = 0;
     for (int w = 0; w < (nt >> 6); ++w) total += added_waves[w];
+    n_extra[b] = total;
+  }
+}
+
+// ------------------------------------------------------------------- ATSS matching
+// Adaptive Training Sample Selection behind match_kernel (mbx_match_atss, mbx.h has the rule): per box the `topk` priors
+// nearest to its centre on every level are its candidates, its threshold is the mean plus the sample standard deviation of
+// their IoUs, and a candidate at or over it whose centre lies inside the box is a positive; a free prior goes to the
+// positive box of the largest IoU, the lowest j among equals.  One workgroup of `nw` wavefronts per image.
+//   LDS: claim[P] (8 B: the largest IoU bit pattern a positive box has claimed the prior with) | boxes[G] (StagedBox) |
+//        iou[nw][m] (8 B, a wavefront's scratch) | cand[G][m] (2 B: a box's candidates, then its positives).
+//   Pass 1, a wavefront per box j = wave, wave + nw, ...: per level it finds the cut -- the min(topk, size)-th smallest
+//     (distance key, index) pair.  A strided scan leaves in every lane's registers the kAtssKeep smallest of its own pairs,
+//     in order; each round a 64-lane min over the heads of the lists takes the next pair.  Only when a lane has handed out
+//     its whole list and had more to offer does the wavefront scan again, for the pairs over the last one taken: with topk
+//     9 and the priors of one cell on neighbouring lanes that is one scan a level, not nine (the launch at P = 3199,
+//     G = 100: 1 159 us with a scan a round, 539 with the lists, 490 with the rounds' minimum on DPP moves, 432 as it is;
+//     profiles/match_atss_bench.txt).  Nothing is marked or stored; a level no larger than topk is taken whole without a
+//     round.  One more scan in 64-prior chunks writes the priors at or under the cut in ascending index (ballot + prefix
+//     count); their IoUs follow, m divisions and not one per prior of the level.  Every lane then runs the two serial sums
+//     over the m IoUs (the same LDS address for all: a broadcast), so the threshold needs no hand-off.
+//     A positive whose prior mbx_match left free raises claim[p] with a 64-bit unsigned LDS
+//     max: IoUs are >= 0, so their bit patterns order like the values and the result does not depend on who came first.
+//     A candidate that is no such positive is struck from cand.
+//   Pass 2, every thread over the G x m entries: a positive whose IoU (the same function on the same inputs: the same
+//     bits) equals claim[p] lowers match[b,p] with an unsigned integer min -- a free entry is negative, as unsigned above
+//     every j -- so the lowest j among the largest IoUs stays; whoever finds the entry still negative counts the prior.
+// Lanes of one wavefront hand LDS values to each other without a workgroup barrier (the wavefronts run different numbers
+// of boxes): wave_lds_sync() keeps the compiler from moving LDS accesses across the hand-off; the hardware runs one
+// wavefront's LDS instructions in order.
+struct AtssLevels { int start[9]; };                          // level_start by value: at most 8 levels
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Squared centre distance of prior q to (cxj, cyj) as an unsigned key: a non-negative double orders like its bit pattern;
+// a NaN goes behind every number, +inf included.
+__device__ __forceinline__ unsigned long long atss_d2_key(const float4 q, double cxj, double cyj) {
+  const double cx = ((double)q.x + (double)q.z) * 0.5, cy = ((double)q.y + (double)q.w) * 0.5;
+  const double dx = cx - cxj, dy = cy - cyj;
+  const double d2 = dx * dx + dy * dy;
+  return d2 != d2 ? ~0ull : (d2 == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(d2));
+}
+
+// (key, index) pairs in lexicographic order: equal distances go to the lowest prior index.
+__device__ __forceinline__ bool atss_pair_less(unsigned long long ka, int ia, unsigned long long kb, int ib) {
+  return ka < kb || (ka == kb && ia < ib);
+}
+
+// The smallest (key, index) pair of the wavefront's 64 lanes, in every lane (all 64 active), by data-parallel-primitive
+// moves.  A step: every lane takes the value of the lane the control CTRL names and keeps the smaller; a lane the control
+// gives no source, or whose row ROW_MASK leaves out, sees the identity (all ones).  A shift scan inside each row of 16
+// lanes (row_shr 1, 2, 4, 8), then lane 15 of rows 0 and 2 to rows 1 and 3 (row_bcast15) and lane 31 to rows 2 and 3
+// (row_bcast31) leave the minimum in lane 63, which is read out as a wavefront-uniform value.  The 64-bit keys are reduced
+// first; one lane holds the smallest key unless distances tie, and only then are the tied lanes' indices reduced too.
+// No LDS traffic: the sixteen wavefronts of a workgroup run these rounds at once, and as ds_bpermute shuffles, eighteen a
+// round, they all went through the one LDS of the compute unit (539 -> 490 us at P = 3199, G = 100; LAB_NOTES).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void atss_dpp_min(unsigned long long& k) {
+  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)k, CTRL, ROW_MASK, 0xf, false);
+  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(k >> 32), CTRL, ROW_MASK, 0xf, false);
+  const unsigned long long ok = ((unsigned long long)ohi << 32) | olo;
+  if (ok < k) k = ok;
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void atss_dpp_min(int& i) {
+  const int oi = __builtin_amdgcn_update_dpp(0x7fffffff, i, CTRL, ROW_MASK, 0xf, false);
+  if (oi < i) i = oi;
+}
+template <typename T>
+__device__ __forceinline__ void atss_dpp_min_to_lane63(T& v) {
+  atss_dpp_min<0x111, 0xf>(v);
+  atss_dpp_min<0x112, 0xf>(v);
+  atss_dpp_min<0x114, 0xf>(v);
+  atss_dpp_min<0x118, 0xf>(v);
+  atss_dpp_min<0x142, 0xa>(v);
+  atss_dpp_min<0x143, 0xc>(v);
+}
+
+__device__ __forceinline__ void atss_wave_min(unsigned long long& k, int& i) {
+  unsigned long long mk = k;
+  atss_dpp_min_to_lane63(mk);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mk, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mk >> 32), 63);
+  mk = ((unsigned long long)hi << 32) | lo;
+  const unsigned long long tied = __ballot(k == mk);          // never empty: the lane the minimum came from
+  int mi;
+  if (__popcll(tied) == 1) {
+    mi = __builtin_amdgcn_readlane(i, __ffsll((long long)tied) - 1);
+  } else {                                                    // equal keys: the lowest index among them
+    mi = k == mk ? i : 0x7fffffff;
+    atss_dpp_min_to_lane63(mi);
+    mi = __builtin_amdgcn_readlane(mi, 63);
+  }
+  k = mk;
+  i = mi;
+}
+
+constexpr unsigned short kAtssNone = 0xffffu;                // P <= 65535: no prior has this index
+constexpr int kAtssKeep = 4;                                  // pairs a lane keeps from one scan (12 registers)
+
+__global__ void __launch_bounds__(1024)
+match_atss_kernel(const float4* __restrict__ priors, const AtssLevels lv, int n_levels, const float4* __restrict__ gt,
+                  const int* __restrict__ n_gt, const int* __restrict__ status, int topk, int m, int P, int G,
+                  int* __restrict__ match, int* __restrict__ n_extra, double* __restrict__ thr_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = (int)blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+  unsigned long long* claim = reinterpret_cast<unsigned long long*>(smem);          // [P]
+  StagedBox* boxes = reinterpret_cast<StagedBox*>(claim + P);                       // [G]
+  double* iou_w = reinterpret_cast<double*>(boxes + G) + (size_t)wave * m;          // [nw][m], this wavefront's row
+  unsigned short* cand = reinterpret_cast<unsigned short*>(reinterpret_cast<double*>(boxes + G) + (size_t)nw * m);   // [G][m]
+  __shared__ int ls[9];
+  __shared__ int added_waves[16];
+  const int n = n_gt[b];
+  if (status[b] != 0 || n <= 0 || n > G) {                    // skipped: the row stays as it is (mbx_match_extend's rule)
+    if (tid == 0 && n_extra) n_extra[b] = 0;
+    if (thr_out) for (int j = tid; j < G; j += nt) thr_out[(size_t)b * G + j] = 0.0;
+    return;
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ls[i] = lv.start[i];
+  }
+  for (int p = tid; p < P; p += nt) claim[p] = 0ull;
+  for (int j = tid; j < n; j += nt) {
+    const float4 q = gt[(size_t)b * G + j];
+    StagedBox s;
+    s.box = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    s.area = box_area(s.box);
+    boxes[j] = s;
+  }
+  if (thr_out) for (int j = n + tid; j < G; j += nt) thr_out[(size_t)b * G + j] = 0.0;
+  __syncthreads();
+  int* mt = match + (size_t)b * P;
+
+  for (int j = wave; j < n; j += nw) {                        // pass 1
+    const StagedBox sb = boxes[j];
+    const double cxj = (sb.box.x1 + sb.box.x2) * 0.5, cyj = (sb.box.y1 + sb.box.y2) * 0.5;
+    unsigned short* cj = cand + (size_t)j * m;
+    int cnt = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      const int lo = ls[l], hi = ls[l + 1];
+      const int c = topk < hi - lo ? topk : hi - lo;
+      unsigned long long cut_k = ~0ull;                       // the whole level: no pair is over (all ones, INT_MAX)
+      int cut_i = 0x7fffffff;
+      if (c < hi - lo) {
+        unsigned long long last_k = 0ull;                     // every pair is over (0, -1)
+        int last_i = -1;
+        int taken = 0;
+        while (taken < c) {
+          // scan: the lane's kAtssKeep smallest pairs over the last one taken, ascending; (all ones, INT_MAX) = none
+          unsigned long long lk[kAtssKeep];
+          int li[kAtssKeep];
+#pragma unroll
+          for (int t = 0; t < kAtssKeep; ++t) { lk[t] = ~0ull; li[t] = 0x7fffffff; }
+          int eligible = 0;                                   // how many of the lane's pairs are over the last one taken
+          auto offer = [&](const float4 q, int p) {
+            const unsigned long long k = atss_d2_key(q, cxj, cyj);
+            if (!atss_pair_less(last_k, last_i, k, p)) return;
+            ++eligible;
+            if (!atss_pair_less(k, p, lk[kAtssKeep - 1], li[kAtssKeep - 1])) return;
+            lk[kAtssKeep - 1] = k; li[kAtssKeep - 1] = p;
+#pragma unroll
+            for (int t = kAtssKeep - 1; t > 0; --t) {
+              if (atss_pair_less(lk[t], li[t], lk[t - 1], li[t - 1])) {
+                const unsigned long long sk = lk[t]; lk[t] = lk[t - 1]; lk[t - 1] = sk;
+                const int si = li[t]; li[t] = li[t - 1]; li[t - 1] = si;
+              }
+            }
+          };
+          for (int p = lo + lane; p < hi; p += 128) {         // two loads in flight: the scan waits on L2, not on arithmetic
+            const int p1 = p + 64;
+            const float4 q0 = priors[p], q1 = priors[p1 < hi ? p1 : p];
+            offer(q0, p);
+            if (p1 < hi) offer(q1, p1);
+          }
+          // rounds: the smallest head of the 64 lists is the next pair; its lane moves on.  A lane that has handed out its
+          // whole list and had more pairs than it could keep no longer knows its smallest: scan again from the last one.
+          int pops = 0;
+          while (taken < c) {
+            if (__any(pops == kAtssKeep && eligible > kAtssKeep)) break;
+            unsigned long long best_k = lk[0];
+            int best_i = li[0];
+            atss_wave_min(best_k, best_i);
+            if (li[0] == best_i) {                            // indices are distinct: the one lane that holds it
+#pragma unroll
+              for (int t = 0; t + 1 < kAtssKeep; ++t) { lk[t] = lk[t + 1]; li[t] = li[t + 1]; }
+              lk[kAtssKeep - 1] = ~0ull; li[kAtssKeep - 1] = 0x7fffffff;
+              ++pops;
+            }
+            last_k = best_k;
+            last_i = best_i;
+            ++taken;
+          }
+        }
+        cut_k = last_k;
+        cut_i = last_i;
+      }
+      for (int base = lo; base < hi; base += 64) {            // the priors at or under the cut, in ascending index
+        const int p = base + lane;
+        const bool in = p < hi && !atss_pair_less(cut_k, cut_i, atss_d2_key(priors[p], cxj, cyj), p);
+        const unsigned long long mask = __ballot(in);
+        const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+        if (in && slot < m) cj[slot] = (unsigned short)p;
+        cnt += __popcll(mask);
+      }
+    }
+    wave_lds_sync();
+    for (int t = lane; t < m; t += 64) {                      // the candidates' IoUs, once for the m of them
+      const float4 q = priors[cj[t]];
+      const Box e = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+      iou_w[t] = iou_corners(e, sb.box, sb.area);
+    }
+    wave_lds_sync();
+    double sum = 0.0;                                         // the statistic: every lane, the same serial order
+    for (int t = 0; t < m; ++t) sum += iou_w[t];
+    const double mean = sum / (double)m;
+    double sq = 0.0;
+    for (int t = 0; t < m; ++t) { const double d = iou_w[t] - mean; sq += d * d; }
+    const double sd = m > 1 ? __dsqrt_rn(sq / (double)(m - 1)) : 0.0;
+    const double thr = mean + sd;
+    if (lane == 0 && thr_out) thr_out[(size_t)b * G + j] = thr;
+    for (int t = lane; t < m; t += 64) {
+      const int p = cj[t];
+      const double iou = iou_w[t];
+      const float4 q = priors[p];
+      const double cx = ((double)q.x + (double)q.z) * 0.5, cy = ((double)q.y + (double)q.w) * 0.5;
+      const bool inside = sb.box.x1 < cx && cx < sb.box.x2 && sb.box.y1 < cy && cy < sb.box.y2;
+      if (iou > 0.0 && iou >= thr && inside && mt[p] < 0)     // a NaN fails both comparisons
+        atomicMax(&claim[p], (unsigned long long)__double_as_longlong(iou));
+      else
+        cj[t] = kAtssNone;
+    }
+    wave_lds_sync();                                          // the next box reuses iou_w
+  }
+  __syncthreads();
+
+  int added = 0;                                              // pass 2
+  for (int e = tid; e < n * m; e += nt) {
+    const int p = cand[e];
+    if (p == kAtssNone) continue;
+    const int j = e / m;
+    const float4 q = priors[p];
+    const Box pe = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    const double iou = iou_corners(pe, boxes[j].box, boxes[j].area);
+    if ((unsigned long long)__double_as_longlong(iou) != claim[p]) continue;
+    const unsigned old = atomicMin(reinterpret_cast<unsigned*>(mt + p), (unsigned)j);
+    if (old & 0x80000000u) ++added;                           // it was still free: counted once
+  }
+  if (!n_extra) return;
+  added = wave_sum(added);
+  if (lane == 0) added_waves[wave] = added;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int w = 0; w < nw; ++w) total += added_waves[w];
     n_extra[b] = total;
   }
 }
@@ -650,6 +909,54 @@ extern "C" int mbx_match_extend(const float* priors, const float* gt, const int3
   hipLaunchKernelGGL(match_extend_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
                      reinterpret_cast<const float4*>(priors), reinterpret_cast<const float4*>(gt), n_gt, status,
                      (double)iou_threshold, P, G, match, n_extra);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
+// The checks of mbx_match_atss that need no GPU, and what the launch is sized by: m = the candidates per box, the wavefronts
+// per image (the most of 16, 8, 4, 2, 1 whose LDS fits a plain launch) and the LDS bytes (mbx.h has the formula).
+static int atss_plan(int P, int G, int n_levels, const int32_t* level_start, int topk, int* m_out, int* waves_out,
+                     size_t* lds_out) {
+  if (!level_start || P <= 0 || G <= 0 || topk < 1 || n_levels < 1 || n_levels > 8) return MBX_ERR_INVALID_ARG;
+  if (level_start[0] != 0 || level_start[n_levels] != P) return MBX_ERR_INVALID_ARG;
+  long long m = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    const int size = level_start[l + 1] - level_start[l];
+    if (level_start[l + 1] <= level_start[l]) return MBX_ERR_INVALID_ARG;
+    m += topk < size ? topk : size;
+  }
+  if (P >= (int)kAtssNone) return MBX_ERR_UNSUPPORTED;       // (8 P alone is over the LDS of a plain launch there)
+  for (int waves = 16; waves >= 1; waves >>= 1) {
+    const long long lds = 8ll * P + (long long)sizeof(StagedBox) * G + 2ll * G * m + 8ll * waves * m;
+    if (lds + 128 <= 64 * 1024) {                             // 128: the kernel's static LDS (112 bytes) rounded up
+      if (m_out) *m_out = (int)m;
+      if (waves_out) *waves_out = waves;
+      if (lds_out) *lds_out = (size_t)lds;
+      return MBX_OK;
+    }
+  }
+  return MBX_ERR_UNSUPPORTED;
+}
+
+extern "C" int mbx_match_atss_supported(int P, int G, int n_levels, const int32_t* level_start, int topk) {
+  return atss_plan(P, G, n_levels, level_start, topk, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mbx_match_atss(const float* priors, const int32_t* level_start, int n_levels, const float* gt,
+                              const int32_t* n_gt, const int32_t* status, int topk, int B, int P, int G, int32_t* match,
+                              int32_t* n_extra, double* thr, mbx_stream_t stream) {
+  if (!priors || !gt || !n_gt || !status || !match || B < 0) return MBX_ERR_INVALID_ARG;
+  int m = 0, waves = 0;
+  size_t lds = 0;
+  const int plan = atss_plan(P, G, n_levels, level_start, topk, &m, &waves, &lds);
+  if (plan != MBX_OK) return plan;
+  if (B == 0) return MBX_OK;
+  AtssLevels lv;
+  for (int i = 0; i < 9; ++i) lv.start[i] = i <= n_levels ? level_start[i] : P;
+  MBX_ENTER();
+  hipLaunchKernelGGL(match_atss_kernel, dim3(B), dim3(waves * 64), lds, mbx_s(stream),
+                     reinterpret_cast<const float4*>(priors), lv, n_levels, reinterpret_cast<const float4*>(gt), n_gt,
+                     status, topk, m, P, G, match, n_extra, thr);
   MBX_LAUNCH_CHECK();
   return MBX_OK;
 }

@@ -61,6 +61,31 @@ def extend_matches(priors, gt_bboxes, num_gt_bboxes, status, match, iou_threshol
     return match, n_extra
 
 
+def _level_table(level_start):
+    """level_start as the int32 HOST array mbx_match_atss takes, and its number of levels."""
+    levels = [int(v) for v in level_start]
+    return (ctypes.c_int32 * len(levels))(*levels), len(levels) - 1
+
+
+def atss_matches(priors, level_start, gt_bboxes, num_gt_bboxes, status, match, topk, n_extra=None, thr=None):
+    """mbx_match_atss (ATSS matching, Zhang et al. 2020): priors [P,4] corners, level_start the HOST list [0, ..., P] of
+    the pyramid levels, gt [B,G,4], n [B], status [B] as mbx_match left it, match int32 [B,P] updated IN PLACE -- per box
+    the topk priors nearest to its centre on every level are candidates, its threshold is the mean plus the standard
+    deviation of their IoUs, and every free prior that is a candidate at or over it with its centre inside the box goes to
+    the box of the largest IoU.  n_extra int32 [B] and thr float64 [B,G] (both optional) receive the number added per
+    image and the thresholds.  Returns (match, n_extra, thr)."""
+    B, P = match.shape
+    G = gt_bboxes.shape[1]
+    assert priors.shape == (P, 4) and gt_bboxes.shape == (B, G, 4)
+    assert thr is None or (thr.is_cuda and thr.dtype == torch.float64 and thr.is_contiguous() and thr.shape == (B, G))
+    table, n_levels = _level_table(level_start)
+    _lib.check(_lib.lib().mbx_match_atss(_f32(priors).data_ptr(), table, n_levels, _f32(gt_bboxes).data_ptr(),
+                                         _i32(num_gt_bboxes).data_ptr(), _i32(status).data_ptr(), int(topk), B, P, G,
+                                         _i32(match).data_ptr(), None if n_extra is None else _i32(n_extra).data_ptr(),
+                                         None if thr is None else thr.data_ptr(), _stream()), "mbx_match_atss")
+    return match, n_extra, thr
+
+
 def compute_assignments(locations, confidences, gt_bboxes, num_gt_bboxes, batch_size, alpha):
     """loss.py:8-53.  Same inputs/outputs as the py_func callback: returns
     [assignment_partitions int32 [B*P], stacked_gt_bboxes float32 [M,4]] (row order),
@@ -131,6 +156,15 @@ class MultiboxLoss:
     (mbx_match_extend, include/mbx.h); the number added per image is left in ``n_extra``.  The loss, mined or not, reads
     the extended ``match``.  What that does to AP on real data is not measured here either.
 
+    atss_topk (an int >= 1; None = off) with prior_levels (the list [0, ..., P] of where each pyramid level of the priors
+    starts, required with it): ATSS matching in the place of threshold matching -- behind mbx_match every box takes the
+    atss_topk priors nearest to its centre on every level as candidates, and the free ones at or over the mean plus the
+    standard deviation of the candidates' IoUs whose centre lies in the box become its positives (mbx_match_atss,
+    include/mbx.h); the number added per image is left in ``n_atss``, the thresholds in ``atss_thr``.  Not together with
+    match_iou_threshold: both decide what a free prior becomes.  With k priors per cell sharing a centre, 9 reaches about
+    two cells of a level at k = 5; the paper's nine locations are 9 * k.  What that does to AP on real data is not measured
+    here either.
+
     focal_gamma (a float in [0, 10]; None = off, the reference's loss): the focal loss on the confidence term -- a
     positive's -log c is weighted by w^gamma and a counted negative's -log w by c^gamma (mbx_loss_fwd_bwd_focal,
     include/mbx.h).  focal_alpha (a float inside (0, 1); None = both sides weigh 1; only with focal_gamma) weighs the
@@ -145,7 +179,8 @@ class MultiboxLoss:
     pass your own.  What any of these does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
-                 min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None):
+                 min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
+                 atss_topk=None, prior_levels=None):
         self.focal = _focal_arguments(focal_gamma, focal_alpha)
         self.loc = _loc_arguments(loc_loss, loc_beta)
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
@@ -185,6 +220,32 @@ class MultiboxLoss:
                 raise ValueError("match_iou_threshold must be in (0, 1], got %r" % (match_iou_threshold,))
             self.match_iou_threshold = float(match_iou_threshold)
             self.n_extra = torch.zeros((self.B,), dtype=torch.int32, device=device)
+        self.atss_topk, self.prior_levels, self.n_atss, self.atss_thr = None, None, None, None
+        if atss_topk is not None:
+            if match_iou_threshold is not None:
+                raise ValueError("atss_topk and match_iou_threshold are both given: each decides what a free prior becomes")
+            if not (isinstance(atss_topk, int) and not isinstance(atss_topk, bool) and 1 <= atss_topk <= 2 ** 31 - 1):
+                raise ValueError("atss_topk must be an int >= 1, got %r" % (atss_topk,))
+            if prior_levels is None:
+                raise ValueError("atss_topk needs prior_levels, the list [0, ..., P] of where each level of the priors starts")
+            try:
+                levels = [int(v) for v in prior_levels]
+            except (TypeError, ValueError):
+                raise ValueError("prior_levels must be a list of ints, got %r" % (prior_levels,))
+            if not (2 <= len(levels) <= 9 and levels[0] == 0 and levels[-1] == self.P
+                    and all(a < b for a, b in zip(levels, levels[1:]))):
+                raise ValueError("prior_levels must hold 1 to 8 levels, start at 0, ascend strictly and end at the %d priors, "
+                                 "got %r" % (self.P, levels))
+            self._level_table, self._n_levels = _level_table(levels)
+            verdict = l.mbx_match_atss_supported(self.P, self.G, self._n_levels, self._level_table, atss_topk)
+            if verdict != 0:
+                raise ValueError("atss_topk %d with prior_levels %r, %d priors and %d boxes an image: mbx_match_atss says %s"
+                                 % (atss_topk, levels, self.P, self.G, l.mbx_status_string(verdict).decode()))
+            self.atss_topk, self.prior_levels = atss_topk, levels
+            self.n_atss = torch.zeros((self.B,), dtype=torch.int32, device=device)
+            self.atss_thr = torch.zeros((self.B, self.G), dtype=torch.float64, device=device)
+        elif prior_levels is not None:
+            raise ValueError("prior_levels is given without atss_topk")
 
     def forward_backward(self, raw_locs, logits, gt_bboxes, num_gt_bboxes, grad_scale=1.0, conf_is_logit=True):
         """raw_locs [B,P,4], logits [B,P] f32 -> (loss2 [2] = {location_loss, confidence_loss}, d_locs, d_logits)."""
@@ -206,6 +267,11 @@ class MultiboxLoss:
             _lib.check(l.mbx_match_extend(self.priors.data_ptr(), gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),
                                           self.status.data_ptr(), self.match_iou_threshold, B, P, G,
                                           self.match.data_ptr(), self.n_extra.data_ptr(), s), "mbx_match_extend")
+        if self.atss_topk is not None:
+            _lib.check(l.mbx_match_atss(self.priors.data_ptr(), self._level_table, self._n_levels, gt_bboxes.data_ptr(),
+                                        num_gt_bboxes.data_ptr(), self.status.data_ptr(), self.atss_topk, B, P, G,
+                                        self.match.data_ptr(), self.n_atss.data_ptr(), self.atss_thr.data_ptr(), s),
+                       "mbx_match_atss")
         common = (self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)), gt_bboxes.data_ptr(),
                   self.match.data_ptr(), self.alpha, float(grad_scale), B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
                   self.d_logits.data_ptr())

@@ -1060,6 +1060,73 @@ int mbx_adam_ema_step(float* w, const float* g, float* m, float* v, float* ema /
                       const int64_t* skipped /*DEVICE, or NULL*/, float ema_decay, int trainable, float* reg_loss,
                       const float* ctl, int clipped, mbx_stream_t stream);
 
+/* Layer-wise trust ratios: LARS on sgd, LAMB on adam / adamw (You, Gitman, Ginsburg 2017; You et al. 2020; not in the
+ * reference; nothing here runs unless asked for).  Every VARIABLE of a trainable range gets its own factor
+ * r = coeff * ||w|| / ||x||, w the weights before the step and x what the rule would subtract:
+ *   sgd          x = g', the optimiser's own g + wd_l2*w in float32, times clip[2] when clipped -- the vector the optimiser
+ *                consumes (the paper's denominator ||g|| + wd*||w|| bounds ||g'|| from above).  The rule consumes r*g':
+ *                acc = momentum*acc + r*g'.
+ *   adam, adamw  x = u = m^ / (sqrt(v^) + eps) + wd_decoupled*w from the UPDATED moments, AdamRule's own expression.  The step
+ *                is w -= lr * (r*u).
+ * A variable ADAPTS iff the caller says so (Trainer: more than one dimension); r is exactly 1.0f when it does not, or when
+ * either norm is 0.  Otherwise r = (float)((double)coeff * sqrt(sum w^2) / sqrt(sum x^2)): both sums in double over float32
+ * values, no epsilon, no special case for a non-finite norm (with clipping the guard skips such a step already).
+ * A ratio of exactly 1.0f changes no bit: w, the slots, ema and w_bf16 are then byte-identical to mbx_sgd_ema_step /
+ * mbx_adam_ema_step on the same range (reg_loss up to the order of its atomics).
+ *
+ * THE PLAN (host only, no device).  The variables of one range form a contiguous partition: bounds (HOST int64[n_vars + 1],
+ * ascending, bounds[0] = 0, range coordinates -- element 0 is what the w, g, ... pointers of the launches point at) and
+ * adapt (HOST int32[n_vars]).  Chunks are cut on the grid of multiples of CH = mbx_trust_chunk_elems() (a power of two, a
+ * multiple of 1024) AND at every variable bound: a chunk lies in one variable, is at most CH long and starts at a multiple
+ * of CH or at a variable bound; chunks are in ascending order, a variable's chunks are consecutive.  mbx_trust_plan_count
+ * returns their number, or 0 for arguments mbx_trust_plan refuses; mbx_trust_plan fills chunks_out[count] and
+ * vars_out[n_vars], two images the caller uploads once (DEVICE copies 8-byte aligned).
+ *
+ * THE PASSES, each one workgroup of 256 per chunk (mbx_trust_ratios: one wavefront per variable), all gated like the step: with
+ * ctl (the step control block, or the CLIP BLOCK when clipped != 0) flagged NOTHING is written -- moments, partials and ratio
+ * keep their contents.  Within a chunk: scalars up to 4-element alignment, 16-byte accesses over the body, scalars for the
+ * tail; element by element throughout when a pointer is not 16-byte aligned (w_bf16: 8-byte).  Variable bounds need no
+ * alignment at all.
+ *   mbx_trust_norms_sgd     partials[2c] = sum w^2, partials[2c + 1] = sum x^2 over chunk c (lane, wavefront, workgroup in a fixed
+ *                           order; no atomics: the same inputs give the same bits).  Reads w and g.
+ *   mbx_trust_moments_adam  the same two sums with x = u, and WRITES the updated m and v (mbx_adam_ema_step's moments and bias
+ *                           correction: calls / skipped as there).
+ *   mbx_trust_ratios        ratio[i] (DEVICE float32[n_vars]) from the slots of variable i's chunks, summed in a fixed order.
+ *   mbx_sgd_ema_step_trust, mbx_adam_ema_step_trust
+ *                           the twins' arguments plus the plan and the ratios: the gate, the EMA from the weight before the
+ *                           step, reg_loss, frozen ranges and the bf16 refresh as in the twins.  n is the range's length (0:
+ *                           MBX_OK, nothing launched); the elements touched are the chunks'.  The adam form recomputes u from
+ *                           the STORED moments and does not update them again: it follows mbx_trust_moments_adam of the same
+ *                           step with the same calls / skipped, and does not read g.
+ * MBX_ERR_INVALID_ARG before any device work: what the twins refuse; n_vars < 1, a null bounds / adapt / output, bounds not
+ * ascending from 0 or with an empty variable; a null or misaligned table, n_chunks or n_vars <= 0 in the norm and ratio passes
+ * (n_chunks < 0 in the apply passes), a null partials or ratio, coeff <= 0, infinite or NaN, clipped != 0 without ctl.
+ * Measured (tools/trust_bench.py, profiles/trust_bench.txt): each pass beside its partner of the same build.  What LARS / LAMB
+ * do to AP or convergence on real data is not measured: no dataset or trained model is at hand.                          */
+typedef struct { int64_t lo; int32_t len; int32_t var; } mbx_trust_chunk;                          /* 16 bytes */
+typedef struct { int32_t first_chunk; int32_t n_chunks; int32_t adapt; int32_t pad; } mbx_trust_var; /* 16 bytes */
+int64_t mbx_trust_chunk_elems(void);
+int64_t mbx_trust_plan_count(const int64_t* bounds /*HOST [n_vars+1]*/, int64_t n_vars);
+int mbx_trust_plan(const int64_t* bounds /*HOST [n_vars+1]*/, const int32_t* adapt /*HOST [n_vars]*/, int64_t n_vars,
+                   mbx_trust_chunk* chunks_out /*HOST*/, mbx_trust_var* vars_out /*HOST*/);
+int mbx_trust_norms_sgd(const float* w, const float* g, const mbx_trust_chunk* chunks, int64_t n_chunks, float wd_l2,
+                        double* partials /*[2*n_chunks]*/, const float* ctl, int clipped, mbx_stream_t stream);
+int mbx_trust_moments_adam(const float* w, const float* g, float* m, float* v, const mbx_trust_chunk* chunks, int64_t n_chunks,
+                           float beta1, float beta2, float eps, float wd_l2, float wd_decoupled, int64_t calls,
+                           const int64_t* skipped /*DEVICE, or NULL*/, double* partials /*[2*n_chunks]*/, const float* ctl,
+                           int clipped, mbx_stream_t stream);
+int mbx_trust_ratios(const double* partials, const mbx_trust_var* vars, int64_t n_vars, float coeff, float* ratio /*[n_vars]*/,
+                     const float* ctl, mbx_stream_t stream);
+int mbx_sgd_ema_step_trust(float* w, const float* g, float* mom /*NULL iff momentum==0*/, float* ema /*or NULL*/,
+                           void* w_bf16 /*or NULL*/, int64_t n, float lr, float momentum, int nesterov, float wd_l2,
+                           float ema_decay, int trainable, float* reg_loss, const float* ctl, int clipped,
+                           const mbx_trust_chunk* chunks, int64_t n_chunks, const float* ratio, mbx_stream_t stream);
+int mbx_adam_ema_step_trust(float* w, const float* g, float* m, float* v, float* ema /*or NULL*/, void* w_bf16 /*or NULL*/,
+                            int64_t n, float lr, float beta1, float beta2, float eps, float wd_l2, float wd_decoupled,
+                            int64_t calls, const int64_t* skipped /*DEVICE, or NULL*/, float ema_decay, int trainable,
+                            float* reg_loss, const float* ctl, int clipped, const mbx_trust_chunk* chunks, int64_t n_chunks,
+                            const float* ratio, mbx_stream_t stream);
+
 /* ------------------------------------------------------------ training input augmentation (row F1)
  * The pixel half of the reference's training input graph (inputs.py:264-351: crop, tf.image.resize_images with a
  * random ResizeMethod, distort_color, random_flip_left_right, (image - 0.5) * 2) for one batch.  The host draws every

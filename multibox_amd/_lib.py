@@ -111,6 +111,14 @@ _SIGS = {
     "mbx_rmsprop_ema_step_clipped": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, I, P, P, P]),
     "mbx_sgd_ema_step": (I, [P, P, P, P, P, C.c_int64, F, F, I, F, F, I, P, P, I, P]),
     "mbx_adam_ema_step": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, C.c_int64, P, F, I, P, P, I, P]),
+    "mbx_trust_chunk_elems": (C.c_int64, []),
+    "mbx_trust_plan_count": (C.c_int64, [P, C.c_int64]),
+    "mbx_trust_plan": (I, [P, P, C.c_int64, P, P]),
+    "mbx_trust_norms_sgd": (I, [P, P, P, C.c_int64, F, P, P, I, P]),
+    "mbx_trust_moments_adam": (I, [P, P, P, P, P, C.c_int64, F, F, F, F, F, C.c_int64, P, P, P, I, P]),
+    "mbx_trust_ratios": (I, [P, P, C.c_int64, F, P, P, P]),
+    "mbx_sgd_ema_step_trust": (I, [P, P, P, P, P, C.c_int64, F, F, I, F, F, I, P, P, I, P, C.c_int64, P, P]),
+    "mbx_adam_ema_step_trust": (I, [P, P, P, P, P, P, C.c_int64, F, F, F, F, F, F, C.c_int64, P, F, I, P, P, I, P, C.c_int64, P, P]),
 }
 
 _lib = None
@@ -135,6 +143,16 @@ class Head(C.Structure):
     """mbx_head (include/mbx.h)."""
     _fields_ = [("h", C.c_void_p), ("ld_h", C.c_int32), ("g", C.c_void_p), ("ld_g", C.c_int32), ("cells", C.c_int32),
                 ("k", C.c_int32), ("off", C.c_int32)]
+
+
+class TrustChunk(C.Structure):
+    """mbx_trust_chunk (include/mbx.h)."""
+    _fields_ = [("lo", C.c_int64), ("len", C.c_int32), ("var", C.c_int32)]
+
+
+class TrustVar(C.Structure):
+    """mbx_trust_var (include/mbx.h)."""
+    _fields_ = [("first_chunk", C.c_int32), ("n_chunks", C.c_int32), ("adapt", C.c_int32), ("pad", C.c_int32)]
 
 
 class FilterEntry(C.Structure):

@@ -33,6 +33,7 @@ SOURCES = {
     "convd.hip": [],
     "convr.hip": [],
     "nnops.hip": ["-munsafe-fp-atomics"],
+    "trust.hip": ["-munsafe-fp-atomics"],
     "bn.hip": ["-munsafe-fp-atomics"],
     "augment.hip": ["-ffp-contract=off"],
 }

@@ -241,3 +241,55 @@ def optimizer(cfg):
         if warmup:
             out["lr_warmup_steps"] = warmup
     return out
+
+
+def trust_coeff_default(optimizer):
+    """LAYERWISE_TRUST_COEFF when absent: LARS's eta under sgd, 1 under adam / adamw (LAMB has no such factor)."""
+    return 0.001 if optimizer == "sgd" else 1.0
+
+
+def check_trust_args(optimizer, layerwise_trust=False, trust_coeff=None):
+    """The ranges layerwise_trust() holds the config keys to, on the Trainer's keyword arguments: raises ValueError naming
+    the argument.  Returns the coefficient in use, or None when the switch is off."""
+    if not isinstance(layerwise_trust, bool):
+        raise ValueError("layerwise_trust must be True or False, got %r" % (layerwise_trust,))
+    if not layerwise_trust:
+        if trust_coeff is not None:
+            raise ValueError("trust_coeff goes with layerwise_trust=True only, got %r" % (trust_coeff,))
+        return None
+    if optimizer not in ("sgd", "adam", "adamw"):
+        raise ValueError("layerwise_trust goes with optimizer sgd (LARS), adam or adamw (LAMB), not with %r" % (optimizer,))
+    if trust_coeff is None:
+        return trust_coeff_default(optimizer)
+    if not (isinstance(trust_coeff, (int, float)) and not isinstance(trust_coeff, bool) and 0 < ctypes.c_float(trust_coeff).value < float("inf")):
+        raise ValueError("trust_coeff must be a finite number > 0 as a float32, got %r" % (trust_coeff,))
+    return float(trust_coeff)
+
+
+def layerwise_trust(cfg):
+    """Layer-wise trust ratios (mbx_trust_* / mbx_sgd_ema_step_trust / mbx_adam_ema_step_trust; not in the reference, so off
+    when absent): None, or a dict of Trainer keyword arguments.
+      LAYERWISE_TRUST        a bool (absent, null or false = off).  Every trainable filter variable with more than one
+        dimension scales its update by LAYERWISE_TRUST_COEFF * ||w|| / ||x||: with OPTIMIZER sgd this is LARS (x = g', the
+        vector the optimiser consumes), with adam / adamw LAMB (x = Adam's update, the decoupled decay included).  Biases and
+        betas keep a ratio of 1.  With OPTIMIZER absent or rmsprop: ValueError.
+      LAYERWISE_TRUST_COEFF  finite and > 0 as a float32, only with LAYERWISE_TRUST: true; default 0.001 under sgd (LARS's
+        eta), 1.0 under adam / adamw.
+    A non-bool switch, a bool, a string, a list, a NaN or a value out of range for the coefficient, or the coefficient
+    without the switch raises ValueError naming the key.  Host code only."""
+    on, coeff = cfg.get("LAYERWISE_TRUST"), cfg.get("LAYERWISE_TRUST_COEFF")
+    if on is not None and not isinstance(on, bool):
+        raise ValueError("LAYERWISE_TRUST must be true or false, got %r" % (on,))
+    if not on:
+        if coeff is not None:
+            raise ValueError("LAYERWISE_TRUST_COEFF goes with LAYERWISE_TRUST: true only, got %r" % (coeff,))
+        return None
+    kind = cfg.get("OPTIMIZER")
+    if kind not in ("sgd", "adam", "adamw"):
+        raise ValueError("LAYERWISE_TRUST goes with OPTIMIZER sgd (LARS), adam or adamw (LAMB), not with OPTIMIZER %s"
+                         % (kind if kind is not None else "absent (rmsprop)",))
+    if coeff is None:
+        return {"layerwise_trust": True, "trust_coeff": trust_coeff_default(kind)}
+    if not (isinstance(coeff, (int, float)) and not isinstance(coeff, bool) and 0 < ctypes.c_float(coeff).value < float("inf")):
+        raise ValueError("LAYERWISE_TRUST_COEFF must be a finite number > 0 as a float32, got %r" % (coeff,))
+    return {"layerwise_trust": True, "trust_coeff": float(coeff)}

@@ -1,7 +1,7 @@
 // libmbx: pooling (fwd/bwd), relu mask, head gather/scatter, input packing, step begin, filter preparation and the fused
 // RMSProp+L2+EMA step with its optional global-norm clipping (batch norm: bn.hip).  All HBM-bound: 16-byte (8 x bf16) accesses per lane along the NHWC channel axis
 // (vec8.h), grid-stride loops capped at 2048 blocks.
-#include "vec8.h"
+#include "optim_rules.h"
 #include <type_traits>
 
 namespace {
@@ -461,9 +461,7 @@ filter_prepare_kernel(const unsigned short* __restrict__ w, unsigned short* __re
 }
 
 // --------------------------------------------------------------------------- optimizer
-// The vector the optimiser consumes, g' = g + wd*w (the L2 regulariser's gradient rides with the loss gradient): ONE
-// expression for the update (rmsprop_ema_kernel) and for the norm that clips it (grad_sqnorm_kernel), so the two cannot drift.
-__device__ __forceinline__ float opt_grad(float g, float wd, float w) { return fmaf(wd, w, g); }
+// (g' = opt_grad(g, wd, w) and the rules beside RMSProp: optim_rules.h)
 // a * b + c in two roundings, whatever -ffp-contract says
 __device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
 #pragma clang fp contract(off)
@@ -623,62 +621,6 @@ clip_finalize_kernel(const double* __restrict__ partials, long long n_slots, dou
 
 inline int sqnorm_grid(long long n) { return grid_for((n + 3) / 4); }
 
-// ------------------------------------------------------------------- optimiser choice (OPTIMIZER: sgd, adam, adamw)
-// The update rules beside RMSProp.  A rule is a host-side struct of hyper-parameters with kSlots (how many per-element slots it
-// keeps) and ready(), which runs once per thread and returns the element functor: new w = f(w, g', slot a, slot b).  Every
-// rounding of a functor is spelled out (fmaf, or a product / quotient / sum that stands alone: there is no a * b + c left for the
-// compiler to contract), so the clipped and unclipped instantiations and the vector and tail paths give the same bits.
-template <bool kMom>
-struct SgdRule {                                             // tf.train.MomentumOptimizer; kMom = false: momentum 0, no slot
-  static constexpr int kSlots = kMom ? 1 : 0;
-  float lr, momentum;
-  int nesterov;
-  __device__ __forceinline__ SgdRule ready() const { return *this; }
-  __device__ __forceinline__ float operator()(float w, float g, float& acc, float&) const {
-    if constexpr (!kMom) {
-      return fmaf(-lr, g, w);                                // w -= lr * g'
-    } else {
-      acc = fmaf(momentum, acc, g);                          // acc = momentum * acc + g'
-      return fmaf(-lr, nesterov ? fmaf(momentum, acc, g) : acc, w);    // w -= lr * acc, or lr * (g' + momentum * acc)
-    }
-  }
-};
-
-// b^t for an integer t >= 0 by squaring, in double (at most 63 rounds, lane-uniform)
-__device__ __forceinline__ double pow_int(double b, long long t) {
-  double r = 1.0;
-  for (; t > 0; t >>= 1, b *= b)
-    if (t & 1) r *= b;
-  return r;
-}
-
-struct AdamRule {                                            // Adam; wd_decoupled != 0: AdamW
-  static constexpr int kSlots = 2;
-  float lr, beta1, beta2, eps, wd_decoupled;
-  long long calls;
-  const long long* skipped;
-  struct Ready {
-    float lr, b1, omb1, b2, omb2, eps, wdd, c1, c2;
-    __device__ __forceinline__ float operator()(float w, float g, float& m, float& v) const {
-      m = fmaf(b1, m, omb1 * g);                             // m = beta1 * m + (1 - beta1) * g'
-      v = fmaf(b2, v, (omb2 * g) * g);                       // v = beta2 * v + (1 - beta2) * g'^2
-      const float mhat = m * c1, vhat = v * c2;              // m / bc1, v / bc2
-      const float denom = sqrtf(vhat) + eps;
-      float upd = mhat / denom;
-      if (wdd != 0.f) upd = fmaf(wdd, w, upd);               // + wd_decoupled * w, the weight before the step
-      return fmaf(-lr, upd, w);
-    }
-  };
-  // The bias corrections 1 / (1 - beta^t), t = the APPLIED steps including this one: the host's launch count less the steps the
-  // device skipped (read before this step's own increment, which comes later on the stream).  Once per thread, in double.
-  __device__ __forceinline__ Ready ready() const {
-    long long t = calls + 1 - (skipped ? *skipped : 0);
-    if (t < 1) t = 1;                                        // calls < *skipped breaks the contract (include/mbx.h): stay defined
-    const double bc1 = 1.0 - pow_int((double)beta1, t), bc2 = 1.0 - pow_int((double)beta2, t);
-    return Ready{lr, beta1, 1.0f - beta1, beta2, 1.0f - beta2, eps, wd_decoupled, (float)(1.0 / bc1), (float)(1.0 / bc2)};
-  }
-};
-
 // rmsprop_ema_kernel's surroundings around a rule: the gate, the EMA from the weight before the step, the regulariser sum, frozen
 // ranges, the bf16 refresh, 16-byte accesses where every stream in use is 16-byte aligned (wb 8-byte) and element by element
 // otherwise and for the n % 4 tail.  s0 / s1: the rule's slots (those beyond Rule::kSlots are never touched and may be NULL).
@@ -768,8 +710,6 @@ int launch_opt(int clipped, float* w, const float* g, float* s0, float* s1, floa
   MBX_LAUNCH_CHECK();
   return MBX_OK;
 }
-
-inline bool in_unit(float b) { return b >= 0.f && b < 1.f; }       // [0, 1); false for a NaN
 
 }  // namespace
 

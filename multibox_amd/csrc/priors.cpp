@@ -84,7 +84,7 @@ extern "C" uint32_t mbx_crc32c(const void* data, uint64_t n, uint32_t crc) {
   return ~c;
 }
 
-extern "C" int mbx_version(void) { return 101; }
+extern "C" int mbx_version(void) { return 102; }
 
 extern "C" const char* mbx_status_string(int status) {
   switch (status) {

@@ -18,7 +18,7 @@ import re
 import torch
 
 from . import _lib
-from .config import check_optimizer_args
+from .config import check_optimizer_args, check_trust_args
 from .engine import Net, WEIGHT_DECAY
 from .loss import MultiboxLoss
 from .dist import BucketReducer
@@ -50,7 +50,8 @@ class Trainer:
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
                  match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
                  clip_gradient_norm=None, optimizer="rmsprop", sgd_momentum=0.9, sgd_nesterov=False, adam_beta1=0.9,
-                 adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0, atss_topk=None):
+                 adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0, atss_topk=None,
+                 layerwise_trust=False, trust_coeff=None):
         assert net.mode == "train"
         self.net = net
         self.pg = process_group
@@ -83,6 +84,8 @@ class Trainer:
         # (for callers that build a Trainer themselves: a bad value is named here, not by the library's argument error at
         # the first launch)
         check_optimizer_args(self.optimizer, sgd_momentum, adam_beta1, adam_beta2, adam_epsilon, adamw_weight_decay)
+        # layerwise_trust: LARS (sgd) / LAMB (adam, adamw) -- None = off, else the coefficient; the plans are built below
+        self.trust_coeff = check_trust_args(self.optimizer, layerwise_trust, trust_coeff)
         self.sgd_momentum, self.sgd_nesterov = float(sgd_momentum), bool(sgd_nesterov)
         self.adam_beta1, self.adam_beta2, self.adam_eps = float(adam_beta1), float(adam_beta2), float(adam_epsilon)
         self.wd_decoupled = float(adamw_weight_decay) if self.optimizer == "adamw" else 0.0
@@ -106,6 +109,10 @@ class Trainer:
         # --trainable_scopes (train.py:152-171): only variables under the given scopes are updated; everything else in
         # the trainable range still gets its EMA / regulariser / bf16 refresh (it stays a model variable)
         self.opt_ranges = self._optimizer_ranges(trainable_scopes)
+        # layer-wise trust: one chunk plan per trainable filter range, uploaded once, with its partial sums and ratios
+        # ({index into opt_ranges: plan}); betas and frozen ranges have none and keep _range_step.  Off: nothing allocated.
+        self._trust_plans = None if self.trust_coeff is None else {
+            i: self._trust_plan(lo, hi) for i, (buf, lo, hi, on) in enumerate(self.opt_ranges) if buf == "W" and on and hi > lo}
         self.gt = torch.zeros((net.B, max_num_bboxes, 4), **f32)
         self.n_gt = torch.zeros((net.B,), dtype=torch.int32, device=net.dev)
         self.images = torch.zeros((net.B, net.S, net.S, 3), **f32)
@@ -219,6 +226,79 @@ class Trainer:
             if cur_on is not None:
                 out.append((buf, cur_lo, hi_buf, cur_on))
         return out
+
+    def _trust_plan(self, lo, hi):
+        """The chunk plan of the trainable filter range [lo, hi) (mbx_trust_plan, include/mbx.h).  Its variables are the
+        entries of net.param_index in W that start inside it; variable i owns [off_i, off_{i+1}): the alignment gap behind a
+        variable and the stem filter's C-padding ride with it (zero in w and g, and they stay zero).  A variable adapts iff
+        its shape has more than one dimension (filters do, residual biases do not)."""
+        net, l = self.net, _lib.lib()
+        ents = sorted((off, name, len(shape) > 1) for name, (buf, off, shape, _) in net.param_index.items()
+                      if buf == "W" and lo <= off < hi)
+        assert ents, "no variable starts in the trainable range [%d, %d)" % (lo, hi)
+        nv = len(ents)
+        bounds = (_lib.C.c_int64 * (nv + 1))(*([0] + [off - lo for off, _, _ in ents[1:]] + [hi - lo]))
+        adapt = (_lib.C.c_int32 * nv)(*[int(a) for _, _, a in ents])
+        nc = int(l.mbx_trust_plan_count(bounds, nv))
+        if nc <= 0:
+            raise _lib.MbxError("mbx_trust_plan_count refused the variables of [%d, %d)" % (lo, hi))
+        chunks, vars_ = (_lib.TrustChunk * nc)(), (_lib.TrustVar * nv)()
+        _lib.check(l.mbx_trust_plan(bounds, adapt, nv, chunks, vars_), "trust_plan")
+        up = lambda a: torch.frombuffer(bytearray(a), dtype=torch.uint8).to(net.dev)
+        return dict(names=[n for _, n, _ in ents], adapt=[a for _, _, a in ents], n_vars=nv, n_chunks=nc, chunks=up(chunks),
+                    vars=up(vars_), partials=torch.zeros((2 * nc,), dtype=torch.float64, device=net.dev),
+                    ratio=torch.ones((nv,), dtype=torch.float32, device=net.dev))
+
+    def trust_ratios(self):
+        """{variable name: trust ratio} of the last applied step over every trainable filter variable (exactly 1.0 for the
+        biases), or None without layerwise_trust -- host sync; call it at logging intervals."""
+        if self._trust_plans is None:
+            return None
+        out = {}
+        for p in self._trust_plans.values():
+            out.update(zip(p["names"], p["ratio"].tolist()))
+        return out
+
+    def trust_ratio_stats(self):
+        """(min, median, max) of the last step's ratios over the ADAPTING variables, or None -- host sync."""
+        if self._trust_plans is None:
+            return None
+        r = sorted(v for p in self._trust_plans.values() for v, a in zip(p["ratio"].tolist(), p["adapt"]) if a)
+        return (r[0], r[len(r) // 2], r[-1]) if r else None
+
+    def _trust_range_step(self, plan, lo, hi, lr, d, gate, clipped, s):
+        """One trainable filter range under layerwise_trust: the norm pass (adam: it also updates the moments), the ratios,
+        the apply pass -- in the place of _range_step's one launch.  No allocation, no host synchronisation."""
+        net, l = self.net, _lib.lib()
+        n, nc = hi - lo, plan["n_chunks"]
+        P = lambda t_, el=4: None if t_ is None else t_.data_ptr() + el * lo
+        w, g, mom, ms, ema, wb = P(net.W), P(net.Wg), P(self.Wmom), P(self.Wms), P(self.Wema), P(net.Wb, 2)
+        chunks, part, ratio = plan["chunks"].data_ptr(), plan["partials"].data_ptr(), plan["ratio"].data_ptr()
+        reg, c = net.reg_loss.data_ptr(), int(clipped)
+        if self.optimizer == "sgd":
+            _lib.check(l.mbx_trust_norms_sgd(w, g, chunks, nc, self.wd_l2, part, gate, c, s), "trust_norms_sgd")
+        else:
+            calls = self.global_step + self._opt_step_offset + self._skipped_seen       # (as _range_step)
+            assert calls >= 0, "optimizer step count out of step with global_step (%d, offset %d)" % (self.global_step, self._opt_step_offset)
+            sk = self.skipped_steps.data_ptr()
+            _lib.check(l.mbx_trust_moments_adam(w, g, mom, ms, chunks, nc, self.adam_beta1, self.adam_beta2, self.adam_eps, self.wd_l2,
+                                                self.wd_decoupled, calls, sk, part, gate, c, s), "trust_moments_adam")
+        _lib.check(l.mbx_trust_ratios(part, plan["vars"].data_ptr(), plan["n_vars"], self.trust_coeff, ratio, gate, s), "trust_ratios")
+        if self.optimizer == "sgd":
+            st = l.mbx_sgd_ema_step_trust(w, g, mom, ema, wb, n, lr, self.sgd_momentum, int(self.sgd_nesterov), self.wd_l2, d, 1, reg,
+                                          gate, c, chunks, nc, ratio, s)
+        else:
+            st = l.mbx_adam_ema_step_trust(w, g, mom, ms, ema, wb, n, lr, self.adam_beta1, self.adam_beta2, self.adam_eps, self.wd_l2,
+                                           self.wd_decoupled, calls, sk, d, 1, reg, gate, c, chunks, nc, ratio, s)
+        _lib.check(st, "%s W (trust%s)" % (self.optimizer, ", clipped" if clipped else ""))
+
+    def _ranges_step(self, lr, d, gate, clipped, s):
+        """The optimiser launches of every range of self.opt_ranges."""
+        for i, (buf, lo, hi, on) in enumerate(self.opt_ranges):
+            if self._trust_plans is not None and i in self._trust_plans:
+                self._trust_range_step(self._trust_plans[i], lo, hi, lr, d, gate, clipped, s)
+            else:
+                self._range_step(buf, lo, hi, on, lr, d, gate, clipped, s)
 
     def broadcast_parameters(self, src=0):
         """Data-parallel start: every rank takes rank `src`'s variables, optimiser slots and EMA shadows (after a
@@ -627,8 +707,7 @@ class Trainer:
         ctl = net.step_ctl.data_ptr()                  # non-zero -> every launch below is a no-op (poisoned step / stop request)
         if self.clip_norm is not None:
             return self._optimizer_clipped(lr, d, s)
-        for buf, lo, hi, on in self.opt_ranges:
-            self._range_step(buf, lo, hi, on, lr, d, ctl, False, s)
+        self._ranges_step(lr, d, ctl, False, s)
         # moving statistics <- this step's batch statistics, and their EMA shadows (train.py:257) from the new values: one gated launch
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
         net.apply_moving_update(net.step_ctl, self.skipped_steps, self.MMema, self.MVema, d)
@@ -653,8 +732,7 @@ class Trainer:
             slot += k
         _lib.check(l.mbx_clip_finalize(self._clip_partials.data_ptr(), max(1, slot), self.clip_norm, net.step_ctl.data_ptr(),
                                        self._clip_block.data_ptr(), self._clip_counts.data_ptr(), s), "clip_finalize")
-        for buf, lo, hi, on in self.opt_ranges:
-            self._range_step(buf, lo, hi, on, lr, d, self._clip_block.data_ptr(), True, s)
+        self._ranges_step(lr, d, self._clip_block.data_ptr(), True, s)
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
         net.apply_moving_update(self._clip_block, self.skipped_steps, self.MMema, self.MVema, d)
         net.prepare_filters()

@@ -48,7 +48,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, grad_clip, optimizer, atss_matching
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, grad_clip, optimizer, atss_matching, layerwise_trust
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -78,6 +78,7 @@ def main():
         loc_term = loc_loss(cfg)                  # [new] LOSS_LOC_TYPE / LOSS_LOC_BETA: the location term, L2 when absent
         clip_norm = grad_clip(cfg)                # [new] CLIP_GRADIENT_NORM: global-norm clipping + non-finite guard, off when absent
         opt = optimizer(cfg)                      # [new] OPTIMIZER (+ its keys) / LEARNING_RATE_WARMUP_STEPS: RMSProp, no warm-up when absent
+        trust = layerwise_trust(cfg)              # [new] LAYERWISE_TRUST (+ _COEFF): LARS on sgd, LAMB on adam / adamw, off when absent
     except ValueError as e:
         raise SystemExit("config: %s" % e)
     torch.cuda.set_device(local_rank)
@@ -102,7 +103,7 @@ def main():
                  neg_per_pos=mining[0] if mining else None, min_neg=mining[1] if mining else 0,
                  match_iou_threshold=match_iou, focal_gamma=focal[0] if focal else None,
                  focal_alpha=focal[1] if focal else None, loc_loss=loc_term[0] if loc_term else None,
-                 loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm, atss_topk=atss_topk, **opt)
+                 loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm, atss_topk=atss_topk, **opt, **(trust or {}))
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -205,6 +206,9 @@ def main():
                 rec["optimizer"] = opt["optimizer"]
             if "lr_warmup_steps" in opt:
                 rec["warmup_steps"] = opt["lr_warmup_steps"]
+            if trust is not None:
+                rec["layerwise_trust"], rec["trust_coeff"] = True, trust["trust_coeff"]
+                rec["trust_ratio_min"], rec["trust_ratio_median"], rec["trust_ratio_max"] = tr.trust_ratio_stats()
             print("global step %d: loss = %.4f (loc %.4f conf %.4f) lr %.6f %.1f img/s" % (tr.global_step, total, loc, conf, tr.lr, ips))
             log.write(json.dumps(rec) + "\n")
             log.flush()

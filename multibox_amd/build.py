@@ -33,6 +33,7 @@ SOURCES = {
     "convd.hip": [],
     "convr.hip": [],
     "nnops.hip": ["-munsafe-fp-atomics"],
+    "optim.hip": ["-munsafe-fp-atomics"],                      # (nnops.hip's flags, where its kernels came from: their roundings depend on them)
     "trust.hip": ["-munsafe-fp-atomics"],
     "bn.hip": ["-munsafe-fp-atomics"],
     "augment.hip": ["-ffp-contract=off"],

@@ -1,8 +1,7 @@
-// libmbx: pooling (fwd/bwd), relu mask, head gather/scatter, input packing, step begin, filter preparation and the fused
-// RMSProp+L2+EMA step with its optional global-norm clipping (batch norm: bn.hip).  All HBM-bound: 16-byte (8 x bf16) accesses per lane along the NHWC channel axis
-// (vec8.h), grid-stride loops capped at 2048 blocks.
-#include "optim_rules.h"
-#include <type_traits>
+// libmbx: pooling (fwd/bwd), relu mask, head gather/scatter, input packing, step begin and filter preparation (batch norm:
+// bn.hip; the optimiser step and global-norm clipping: optim.hip).  All HBM-bound: 16-byte (8 x bf16) accesses per lane along
+// the NHWC channel axis (vec8.h), grid-stride loops capped at 2048 blocks.
+#include "vec8.h"
 
 namespace {
 
@@ -460,257 +459,6 @@ filter_prepare_kernel(const unsigned short* __restrict__ w, unsigned short* __re
   }
 }
 
-// --------------------------------------------------------------------------- optimizer
-// (g' = opt_grad(g, wd, w) and the rules beside RMSProp: optim_rules.h)
-// a * b + c in two roundings, whatever -ffp-contract says
-__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
-#pragma clang fp contract(off)
-  return a * b + c;
-}
-
-// kClip: skip_ctl is the CLIP BLOCK of clip_finalize_kernel (words [0], [1] the step control block as below, [2] the scale)
-// and the trainable branch uses clip[2] * g'.  A scale of exactly 1.0f changes no bit.
-template <bool kClip>
-__global__ void __launch_bounds__(kT)
-rmsprop_ema_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ ms, float* __restrict__ mom,
-                   float* __restrict__ ema, unsigned short* __restrict__ wb, long long n, float lr, float decay,
-                   float momentum, float eps, float wd, float ema_decay, int trainable, float* __restrict__ reg_loss,
-                   const float* __restrict__ skip_ctl) {
-  // step control block (two floats, summed over ranks with the beta gradients): [0] grid-barrier timeouts of this
-  // step's one-launch BN backward (its gradients are poisoned), [1] ranks that asked to stop (input exhausted).
-  // Either non-zero: the step is NOT applied -- no update, no EMA, nothing written (uniform branch).
-  if (skip_ctl && (skip_ctl[0] != 0.f || skip_ctl[1] != 0.f)) return;
-  float sq = 0.f;
-  float scale = 1.f;
-  if constexpr (kClip) scale = skip_ctl[2];
-  // one element; returns the new weight.  Every rounding is spelled out, so that both instantiations round alike whatever the
-  // compiler's contraction would make of the plain expressions: they are the roundings this kernel has always had --
-  // fused multiply-adds, except that the element-by-element path (fuse_ms = false_type) rounds decay * ms on its own.
-  auto one = [&](auto fuse_ms, float wi, const float gi_, float& msi, float& momi, float& emai) -> float {
-    sq = fmaf(wi, wi, sq);
-    if (ema) emai = fmaf(-(1.0f - ema_decay), emai - wi, emai);       // emai - (1 - ema_decay) * (emai - wi)
-    if (trainable) {
-      float gi = opt_grad(gi_, wd, wi);
-      if constexpr (kClip) gi = scale * gi;
-      const float gg = (1.0f - decay) * gi * gi;
-      const float m = decltype(fuse_ms)::value ? fmaf(decay, msi, gg) : mul_add_unfused(decay, msi, gg);   // decay * ms + (1 - decay) * gi^2
-      msi = m;
-      float step = lr * gi / sqrtf(m + eps);
-      if (mom) { step = fmaf(momentum, momi, step); momi = step; }
-      wi -= step;
-    }
-    return wi;
-  };
-  // 16-byte accesses where every stream is 16-byte aligned (the flat parameter buffers are; round 6: the 4-byte form streamed
-  // 1.8 GB per step at 5.5 TB/s), element by element otherwise
-  const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(ms) |
-                     reinterpret_cast<uintptr_t>(mom) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0 && (reinterpret_cast<uintptr_t>(wb) & 7) == 0;
-  const long long n4 = vec ? n / 4 : 0;
-  const std::true_type vec_path{};
-  const std::false_type tail_path{};
-  for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n4; i += (long long)gridDim.x * kT) {
-    float4 wv = reinterpret_cast<const float4*>(w)[i];
-    float4 ev = ema ? reinterpret_cast<const float4*>(ema)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), mv = gv, ov = gv;
-    if (trainable) { gv = reinterpret_cast<const float4*>(g)[i]; mv = reinterpret_cast<const float4*>(ms)[i]; if (mom) ov = reinterpret_cast<const float4*>(mom)[i]; }
-    wv.x = one(vec_path, wv.x, gv.x, mv.x, ov.x, ev.x); wv.y = one(vec_path, wv.y, gv.y, mv.y, ov.y, ev.y);
-    wv.z = one(vec_path, wv.z, gv.z, mv.z, ov.z, ev.z); wv.w = one(vec_path, wv.w, gv.w, mv.w, ov.w, ev.w);
-    if (ema) reinterpret_cast<float4*>(ema)[i] = ev;
-    if (trainable) { reinterpret_cast<float4*>(ms)[i] = mv; if (mom) reinterpret_cast<float4*>(mom)[i] = ov; reinterpret_cast<float4*>(w)[i] = wv; }
-    if (wb) reinterpret_cast<uint2*>(wb)[i] = make_uint2(pack2bf(wv.x, wv.y), pack2bf(wv.z, wv.w));
-  }
-  for (long long i = 4 * n4 + (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
-    float msi = trainable ? ms[i] : 0.f, momi = (trainable && mom) ? mom[i] : 0.f, emai = ema ? ema[i] : 0.f;
-    const float wi = one(tail_path, w[i], trainable ? g[i] : 0.f, msi, momi, emai);
-    if (ema) ema[i] = emai;
-    if (trainable) { ms[i] = msi; if (mom) mom[i] = momi; w[i] = wi; }
-    if (wb) wb[i] = (unsigned short)f2bf(wi);
-  }
-  if (reg_loss && wd != 0.f) {
-    sq = wave_sum(sq);
-    __shared__ float red[kT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int i = 0; i < kT / 64; ++i) t += red[i];
-      atomicAdd(reg_loss, 0.5f * wd * t);
-    }
-  }
-}
-
-__global__ void __launch_bounds__(kT)
-ema_update_kernel(float* __restrict__ ema, const float* __restrict__ v, long long n, float d,
-                  const float* __restrict__ skip_ctl) {
-  if (skip_ctl && (skip_ctl[0] != 0.f || skip_ctl[1] != 0.f)) return;       // as rmsprop_ema_kernel
-  for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
-    const float e = ema[i];
-    ema[i] = e - (1.0f - d) * (e - v[i]);
-  }
-}
-
-// ------------------------------------------------------------------- global-norm clipping
-// Sum of g'^2 over one range, one double per workgroup in its own slot: no atomics, so the result does not depend on the order
-// the workgroups arrive in.  The grid (sqnorm_grid) and the thread-to-element mapping are fixed functions of n and of the
-// pointers' alignment.  A streaming read: 16-byte loads where g and w are 16-byte aligned (rmsprop_ema_kernel's rule), two
-// grid strides per iteration (four independent loads per lane; 2048 x 256 lanes x 64 B = 128 KiB in flight per CU), element by
-// element otherwise and for the tail.  g' is rounded to float32 like the optimiser's, then widened: 3e19^2 overflows a float.
-// kW: the range has a decay term (w is read); a compile-time switch -- a run-time "load or zero" per element turns the
-// 16-byte loads of w into four guarded 4-byte ones.
-template <bool kW>
-__global__ void __launch_bounds__(kT)
-grad_sqnorm_kernel(const float* __restrict__ g, const float* __restrict__ w, long long n, float wd, double* __restrict__ partials) {
-  double acc = 0.0;
-  auto add = [&](float gi, float wi) { const double v = (double)opt_grad(gi, wd, wi); acc += v * v; };
-  auto add4 = [&](const float4 a, const float4 b) { add(a.x, b.x); add(a.y, b.y); add(a.z, b.z); add(a.w, b.w); };
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
-  const long long n4 = vec ? n / 4 : 0, stride = (long long)gridDim.x * kT;
-  const float4* g4 = reinterpret_cast<const float4*>(g);
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  long long i = (long long)blockIdx.x * kT + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 ga = g4[i], gb = g4[i + stride];
-    const float4 wa = kW ? w4[i] : z4, wb = kW ? w4[i + stride] : z4;
-    add4(ga, wa);
-    add4(gb, wb);
-  }
-  if (i < n4) add4(g4[i], kW ? w4[i] : z4);
-  for (i = 4 * n4 + (long long)blockIdx.x * kT + threadIdx.x; i < n; i += stride) add(g[i], kW ? w[i] : 0.f);
-  acc = wave_sum(acc);
-  __shared__ double red[kT / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int j = 0; j < kT / 64; ++j) t += red[j];
-    partials[blockIdx.x] = t;
-  }
-}
-
-// One workgroup: the slots of every range in a fixed order (thread-strided, wavefront butterfly, four wavefronts in order),
-// then the clip block.  Everything in double; see mbx_clip_finalize (include/mbx.h) for the words.
-__global__ void __launch_bounds__(kT)
-clip_finalize_kernel(const double* __restrict__ partials, long long n_slots, double max_norm, const float* __restrict__ ctl,
-                     float* __restrict__ clip, long long* __restrict__ counts) {
-  double acc = 0.0;
-  for (long long i = threadIdx.x; i < n_slots; i += kT) acc += partials[i];
-  acc = wave_sum(acc);
-  __shared__ double red[kT / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double total = 0.0;
-  for (int j = 0; j < kT / 64; ++j) total += red[j];
-  const float c0 = ctl[0], c1 = ctl[1];
-  const bool finite = total - total == 0.0;                  // false for an infinite and for a NaN sum
-  const double norm = sqrt(total);
-  const bool clipped = finite && norm > max_norm;
-  const double scale = clipped ? max_norm / norm : 1.0;
-  clip[0] = c0;
-  clip[1] = c1 + (finite ? 0.f : 1.f);
-  clip[2] = (float)scale;
-  clip[3] = (float)norm;
-  clip[4] = clipped ? 1.f : 0.f;
-  clip[5] = clip[6] = clip[7] = 0.f;
-  if (c0 == 0.f && c1 == 0.f) {                              // an already flagged step has its cause: count nothing
-    if (clipped) counts[0] += 1;
-    if (!finite) counts[1] += 1;
-  }
-}
-
-inline int sqnorm_grid(long long n) { return grid_for((n + 3) / 4); }
-
-// rmsprop_ema_kernel's surroundings around a rule: the gate, the EMA from the weight before the step, the regulariser sum, frozen
-// ranges, the bf16 refresh, 16-byte accesses where every stream in use is 16-byte aligned (wb 8-byte) and element by element
-// otherwise and for the n % 4 tail.  s0 / s1: the rule's slots (those beyond Rule::kSlots are never touched and may be NULL).
-// kClip: ctl is the clip block and g' = clip[2] * g'.  A pure streaming pass: no LDS beyond the regulariser's four partial sums.
-template <bool kClip, class Rule>
-__global__ void __launch_bounds__(kT)
-opt_ema_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
-               float* __restrict__ ema, unsigned short* __restrict__ wb, long long n, float wd, float ema_decay, int trainable,
-               float* __restrict__ reg_loss, const float* __restrict__ ctl, const Rule rule) {
-  if (ctl && (ctl[0] != 0.f || ctl[1] != 0.f)) return;       // as rmsprop_ema_kernel
-  constexpr bool kA = Rule::kSlots >= 1, kB = Rule::kSlots >= 2;
-  float sq = 0.f;
-  float scale = 1.f;
-  if constexpr (kClip) scale = ctl[2];
-  const auto step = rule.ready();
-  auto one = [&](float wi, const float gi_, float& ai, float& bi, float& emai) -> float {
-    sq = fmaf(wi, wi, sq);
-    if (ema) emai = fmaf(-(1.0f - ema_decay), emai - wi, emai);       // emai - (1 - ema_decay) * (emai - wi)
-    if (trainable) {
-      float gi = opt_grad(gi_, wd, wi);
-      if constexpr (kClip) gi = scale * gi;
-      wi = step(wi, gi, ai, bi);
-    }
-    return wi;
-  };
-  const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | (kA ? reinterpret_cast<uintptr_t>(s0) : 0) |
-                     (kB ? reinterpret_cast<uintptr_t>(s1) : 0) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(wb) & 7) == 0;
-  const long long n4 = vec ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * kT + threadIdx.x; i < n4; i += (long long)gridDim.x * kT) {
-    float4 wv = reinterpret_cast<const float4*>(w)[i];
-    float4 ev = ema ? reinterpret_cast<const float4*>(ema)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), av = gv, bv = gv;
-    if (trainable) {
-      gv = reinterpret_cast<const float4*>(g)[i];
-      if constexpr (kA) av = reinterpret_cast<const float4*>(s0)[i];
-      if constexpr (kB) bv = reinterpret_cast<const float4*>(s1)[i];
-    }
-    wv.x = one(wv.x, gv.x, av.x, bv.x, ev.x); wv.y = one(wv.y, gv.y, av.y, bv.y, ev.y);
-    wv.z = one(wv.z, gv.z, av.z, bv.z, ev.z); wv.w = one(wv.w, gv.w, av.w, bv.w, ev.w);
-    if (ema) reinterpret_cast<float4*>(ema)[i] = ev;
-    if (trainable) {
-      if constexpr (kA) reinterpret_cast<float4*>(s0)[i] = av;
-      if constexpr (kB) reinterpret_cast<float4*>(s1)[i] = bv;
-      reinterpret_cast<float4*>(w)[i] = wv;
-    }
-    if (wb) reinterpret_cast<uint2*>(wb)[i] = make_uint2(pack2bf(wv.x, wv.y), pack2bf(wv.z, wv.w));
-  }
-  for (long long i = 4 * n4 + (long long)blockIdx.x * kT + threadIdx.x; i < n; i += (long long)gridDim.x * kT) {
-    float ai = 0.f, bi = 0.f, emai = ema ? ema[i] : 0.f;
-    if (trainable) {
-      if constexpr (kA) ai = s0[i];
-      if constexpr (kB) bi = s1[i];
-    }
-    const float wi = one(w[i], trainable ? g[i] : 0.f, ai, bi, emai);
-    if (ema) ema[i] = emai;
-    if (trainable) {
-      if constexpr (kA) s0[i] = ai;
-      if constexpr (kB) s1[i] = bi;
-      w[i] = wi;
-    }
-    if (wb) wb[i] = (unsigned short)f2bf(wi);
-  }
-  if (reg_loss && wd != 0.f) {
-    sq = wave_sum(sq);
-    __shared__ float red[kT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int i = 0; i < kT / 64; ++i) t += red[i];
-      atomicAdd(reg_loss, 0.5f * wd * t);
-    }
-  }
-}
-
-template <class Rule>
-int launch_opt(int clipped, float* w, const float* g, float* s0, float* s1, float* ema, void* w_bf16, long long n, float wd,
-               float ema_decay, int trainable, float* reg_loss, const float* ctl, const Rule& rule, mbx_stream_t stream) {
-  MBX_ENTER();
-  if (clipped)
-    hipLaunchKernelGGL((opt_ema_kernel<true, Rule>), dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, s0, s1, ema, (us)w_bf16, n, wd,
-                       ema_decay, trainable, reg_loss, ctl, rule);
-  else
-    hipLaunchKernelGGL((opt_ema_kernel<false, Rule>), dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, s0, s1, ema, (us)w_bf16, n, wd,
-                       ema_decay, trainable, reg_loss, ctl, rule);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
 }  // namespace
 
 // ================================================================================== C ABI
@@ -873,91 +621,6 @@ extern "C" int mbx_filter_prepare(const void* w_bf16, void* w_dgrad, const mbx_f
   MBX_ENTER();
   hipLaunchKernelGGL(filter_prepare_kernel, dim3(total_blocks), dim3(kT), 0, mbx_s(stream), (cus)w_bf16, (us)w_dgrad, table,
                      n_entries);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
-extern "C" int mbx_rmsprop_ema_step(float* w, const float* g, float* ms, float* mom, float* ema, void* w_bf16, int64_t n,
-                                    float lr, float decay, float momentum, float eps, float wd, float ema_decay,
-                                    int trainable, float* reg_loss, const float* skip_ctl, mbx_stream_t stream) {
-  if (!w || n <= 0 || (trainable && (!g || !ms))) return MBX_ERR_INVALID_ARG;
-  if (trainable && momentum != 0.f && !mom) return MBX_ERR_INVALID_ARG;
-  MBX_ENTER();
-  hipLaunchKernelGGL(rmsprop_ema_kernel<false>, dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, ms, momentum != 0.f ? mom : nullptr,
-                     ema, (us)w_bf16, (long long)n, lr, decay, momentum, eps, wd, ema_decay, trainable, reg_loss, skip_ctl);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
-extern "C" int mbx_rmsprop_ema_step_clipped(float* w, const float* g, float* ms, float* mom, float* ema, void* w_bf16, int64_t n,
-                                            float lr, float decay, float momentum, float eps, float wd, float ema_decay,
-                                            int trainable, float* reg_loss, const float* clip, mbx_stream_t stream) {
-  if (!w || n <= 0 || (trainable && (!g || !ms)) || !clip) return MBX_ERR_INVALID_ARG;
-  if (trainable && momentum != 0.f && !mom) return MBX_ERR_INVALID_ARG;
-  MBX_ENTER();
-  hipLaunchKernelGGL(rmsprop_ema_kernel<true>, dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), w, g, ms, momentum != 0.f ? mom : nullptr,
-                     ema, (us)w_bf16, (long long)n, lr, decay, momentum, eps, wd, ema_decay, trainable, reg_loss, clip);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
-extern "C" int64_t mbx_grad_sqnorm_partials(int64_t n) { return n > 0 ? sqnorm_grid(n) : 0; }
-
-extern "C" int mbx_grad_sqnorm(const float* g, const float* w, int64_t n, float wd, double* partials, mbx_stream_t stream) {
-  if (!g || n <= 0 || !partials || (reinterpret_cast<uintptr_t>(partials) & 7) || !(wd == wd) || (wd != 0.f && !w))
-    return MBX_ERR_INVALID_ARG;
-  MBX_ENTER();
-  if (wd != 0.f)
-    hipLaunchKernelGGL(grad_sqnorm_kernel<true>, dim3(sqnorm_grid(n)), dim3(kT), 0, mbx_s(stream), g, w, (long long)n, wd, partials);
-  else
-    hipLaunchKernelGGL(grad_sqnorm_kernel<false>, dim3(sqnorm_grid(n)), dim3(kT), 0, mbx_s(stream), g, (const float*)nullptr,
-                       (long long)n, 0.f, partials);
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
-extern "C" int mbx_clip_finalize(const double* partials, int64_t n_slots, double max_norm, const float* ctl, float* clip,
-                                 int64_t* counts, mbx_stream_t stream) {
-  if (!partials || n_slots <= 0 || !(max_norm > 0.0) || !ctl || !clip || !counts || (reinterpret_cast<uintptr_t>(partials) & 7))
-    return MBX_ERR_INVALID_ARG;
-  MBX_ENTER();
-  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(kT), 0, mbx_s(stream), partials, (long long)n_slots, max_norm, ctl, clip,
-                     reinterpret_cast<long long*>(counts));
-  MBX_LAUNCH_CHECK();
-  return MBX_OK;
-}
-
-extern "C" int mbx_sgd_ema_step(float* w, const float* g, float* mom, float* ema, void* w_bf16, int64_t n, float lr, float momentum,
-                                int nesterov, float wd_l2, float ema_decay, int trainable, float* reg_loss, const float* ctl,
-                                int clipped, mbx_stream_t stream) {
-  if (!w || n < 0 || (trainable && !g) || !in_unit(momentum) || (mom != nullptr) != (momentum != 0.f) || !(wd_l2 >= 0.f) ||
-      (clipped && !ctl))
-    return MBX_ERR_INVALID_ARG;
-  if (n == 0) return MBX_OK;
-  if (mom)
-    return launch_opt(clipped, w, g, mom, nullptr, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
-                      SgdRule<true>{lr, momentum, nesterov}, stream);
-  return launch_opt(clipped, w, g, nullptr, nullptr, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
-                    SgdRule<false>{lr, 0.f, 0}, stream);
-}
-
-extern "C" int mbx_adam_ema_step(float* w, const float* g, float* m, float* v, float* ema, void* w_bf16, int64_t n, float lr,
-                                 float beta1, float beta2, float eps, float wd_l2, float wd_decoupled, int64_t calls,
-                                 const int64_t* skipped, float ema_decay, int trainable, float* reg_loss, const float* ctl,
-                                 int clipped, mbx_stream_t stream) {
-  if (!w || n < 0 || (trainable && (!g || !m || !v)) || !in_unit(beta1) || !in_unit(beta2) || !(eps > 0.f) || !(wd_l2 >= 0.f) ||
-      !(wd_decoupled >= 0.f) || calls < 0 || (clipped && !ctl))
-    return MBX_ERR_INVALID_ARG;
-  if (n == 0) return MBX_OK;
-  return launch_opt(clipped, w, g, m, v, ema, w_bf16, n, wd_l2, ema_decay, trainable, reg_loss, ctl,
-                    AdamRule{lr, beta1, beta2, eps, wd_decoupled, (long long)calls, reinterpret_cast<const long long*>(skipped)}, stream);
-}
-
-extern "C" int mbx_ema_update(float* ema, const float* value, int64_t n, float ema_decay, const float* skip_ctl,
-                              mbx_stream_t stream) {
-  if (!ema || !value || n <= 0) return MBX_ERR_INVALID_ARG;
-  MBX_ENTER();
-  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n)), dim3(kT), 0, mbx_s(stream), ema, value, (long long)n, ema_decay, skip_ctl);
   MBX_LAUNCH_CHECK();
   return MBX_OK;
 }

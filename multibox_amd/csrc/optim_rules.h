@@ -1,22 +1,48 @@
-// The optimiser's element rules, shared by the flat streaming kernels (nnops.hip) and the layer-wise trust kernels (trust.hip):
-// ONE copy of g', of each rule and of Adam's bias correction, so that the two sets of kernels cannot drift apart.
+// The optimiser's element rules, shared by the flat streaming kernels (optim.hip) and the layer-wise trust kernels (trust.hip):
+// ONE copy of g', of each rule and of Adam's bias correction, so that the two sets of kernels cannot drift apart.  What stands
+// around a rule in a kernel (loads, EMA, stores, the regulariser's sum): optim_body.h.
 #pragma once
 #include "vec8.h"
+#include <type_traits>
 
 namespace {
 
 // The vector the optimiser consumes, g' = g + wd*w (the L2 regulariser's gradient rides with the loss gradient): ONE
-// expression for the update (rmsprop_ema_kernel) and for the norm that clips it (grad_sqnorm_kernel), so the two cannot drift.
+// expression for the update (opt_ema_kernel) and for the norm that clips it (grad_sqnorm_kernel), so the two cannot drift.
 __device__ __forceinline__ float opt_grad(float g, float wd, float w) { return fmaf(wd, w, g); }
 
-// ------------------------------------------------------------------- optimiser choice (OPTIMIZER: sgd, adam, adamw)
-// The update rules beside RMSProp.  A rule is a host-side struct of hyper-parameters with kSlots (how many per-element slots it
-// keeps) and ready(), which runs once per thread and returns the element functor: new w = f(w, g', slot a, slot b).  Every
-// rounding of a functor is spelled out (fmaf, or a product / quotient / sum that stands alone: there is no a * b + c left for the
-// compiler to contract), so the clipped and unclipped instantiations and the vector and tail paths give the same bits.
+// a * b + c in two roundings, whatever -ffp-contract says
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
+// ------------------------------------------------------------- optimiser choice (OPTIMIZER: rmsprop, sgd, adam, adamw)
+// A rule is a host-side struct of hyper-parameters with kSlots (how many per-element slots it keeps) and ready(), which runs
+// once per thread and returns the element functor: new w = f(path, w, g', slot a, slot b).  Every rounding of a functor is
+// spelled out (fmaf, or a product / quotient / sum that stands alone: there is no a * b + c left for the compiler to contract),
+// so the clipped and unclipped instantiations give the same bits.  path: std::true_type on the 16-byte path, std::false_type
+// element by element -- known at compile time, and only RmsRule looks at it; sgd and adam give the same bits on both.
 // Layer-wise trust (trust.hip) adds trust(w, g', a, b, r): the same step with the variable's ratio r applied -- to g' under sgd
 // (LARS), to the update under adam (LAMB).  r == 1.0f changes no bit.  kTrustReadsG / kTrustWritesSlots: whether the trusted
 // apply pass needs g and writes the slots (adam: neither -- mbx_trust_moments_adam has already updated the moments).
+template <bool kMom>
+struct RmsRule {                                             // tf.train.RMSPropOptimizer; kMom = false: momentum 0, one slot
+  static constexpr int kSlots = kMom ? 2 : 1;                // slot 0 the mean square, slot 1 the momentum accumulator
+  float lr, decay, momentum, eps;
+  __device__ __forceinline__ RmsRule ready() const { return *this; }
+  // the roundings this step has always had -- fused multiply-adds, except that the element-by-element path rounds decay * ms
+  // on its own
+  template <bool kVec>
+  __device__ __forceinline__ float operator()(std::bool_constant<kVec>, float w, float g, float& ms, float& mom) const {
+    const float gg = (1.0f - decay) * g * g;
+    ms = kVec ? fmaf(decay, ms, gg) : mul_add_unfused(decay, ms, gg);   // decay * ms + (1 - decay) * g'^2
+    float step = lr * g / sqrtf(ms + eps);
+    if constexpr (kMom) { step = fmaf(momentum, mom, step); mom = step; }
+    return w - step;
+  }
+};
+
 template <bool kMom>
 struct SgdRule {                                             // tf.train.MomentumOptimizer; kMom = false: momentum 0, no slot
   static constexpr int kSlots = kMom ? 1 : 0;
@@ -24,7 +50,7 @@ struct SgdRule {                                             // tf.train.Momentu
   float lr, momentum;
   int nesterov;
   __device__ __forceinline__ SgdRule ready() const { return *this; }
-  __device__ __forceinline__ float operator()(float w, float g, float& acc, float&) const {
+  __device__ __forceinline__ float operator()(bool, float w, float g, float& acc, float&) const {
     if constexpr (!kMom) {
       return fmaf(-lr, g, w);                                // w -= lr * g'
     } else {
@@ -32,7 +58,7 @@ struct SgdRule {                                             // tf.train.Momentu
       return fmaf(-lr, nesterov ? fmaf(momentum, acc, g) : acc, w);    // w -= lr * acc, or lr * (g' + momentum * acc)
     }
   }
-  __device__ __forceinline__ float trust(float w, float g, float& acc, float& b, float r) const { return (*this)(w, r * g, acc, b); }
+  __device__ __forceinline__ float trust(float w, float g, float& acc, float& b, float r) const { return (*this)(true, w, r * g, acc, b); }
 };
 
 // b^t for an integer t >= 0 by squaring, in double (at most 63 rounds, lane-uniform)
@@ -63,7 +89,7 @@ struct AdamRule {                                            // Adam; wd_decoupl
       if (wdd != 0.f) upd = fmaf(wdd, w, upd);               // + wd_decoupled * w, the weight before the step
       return upd;
     }
-    __device__ __forceinline__ float operator()(float w, float g, float& m, float& v) const {
+    __device__ __forceinline__ float operator()(bool, float w, float g, float& m, float& v) const {
       moments(g, m, v);
       return fmaf(-lr, update(w, m, v), w);
     }

@@ -3,10 +3,10 @@
 // bound, so a chunk lies in one variable.  One workgroup of kT owns one chunk in every pass:
 //   norm pass    two sums of squares per chunk in double, each into its own slot -- no atomics
 //   ratios       one wavefront per variable sums that variable's slots in a fixed order
-//   apply pass   opt_ema_kernel's element body (optim_rules.h: the same rules) with the variable's ratio
+//   apply pass   opt_ema_kernel's element body (optim_body.h; optim_rules.h: the same rules) with the variable's ratio
 // All HBM-bound streams: 16-byte accesses over the body of a chunk, scalars for the head up to 4-element alignment and for
 // the tail; element by element throughout when a pointer is not 16-byte aligned.
-#include "optim_rules.h"
+#include "optim_body.h"
 
 namespace {
 
@@ -14,8 +14,6 @@ constexpr int kChunk = 8192;                                 // elements; 8 x 16
 
 typedef mbx_trust_chunk Chunk;
 typedef mbx_trust_var Var;
-
-__device__ __forceinline__ bool gated(const float* ctl) { return ctl && (ctl[0] != 0.f || ctl[1] != 0.f); }
 
 // The split of one chunk: [0, head) scalars, n4 16-byte groups from lo + head (a multiple of 4 in range coordinates: 16-byte
 // aligned where the range base is), the rest scalars.  vec = false: everything is head.
@@ -27,19 +25,11 @@ __device__ __forceinline__ Split split_of(const Chunk& c, bool vec) {
   return Split{head, (c.len - head) >> 2};
 }
 
-// two doubles of a workgroup into slots[0], slots[1]: lanes by butterfly, the four wavefronts in order
-__device__ __forceinline__ void block_sum2(double a, double b, double* __restrict__ slots) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  __shared__ double red[2][kT / 64];
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double ta = 0.0, tb = 0.0;
-    for (int j = 0; j < kT / 64; ++j) { ta += red[0][j]; tb += red[1][j]; }
-    slots[0] = ta;
-    slots[1] = tb;
-  }
+// the two sums of this workgroup's chunk (block_sum: a fixed order) into the chunk's own slots
+__device__ __forceinline__ void store_sums(double (&acc)[2], double* __restrict__ partials) {
+  if (!block_sum(acc)) return;
+  partials[2 * (long long)blockIdx.x] = acc[0];
+  partials[2 * (long long)blockIdx.x + 1] = acc[1];
 }
 
 // sgd: sum w^2 and sum x^2, x = clip[2] * g' in float32 (the optimiser's own expression), widened and squared in double
@@ -51,11 +41,11 @@ trust_norms_sgd_kernel(const float* __restrict__ w, const float* __restrict__ g,
   const Chunk c = chunks[blockIdx.x];
   const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
   const Split sp = split_of(c, vec);
-  double aw = 0.0, ax = 0.0;
+  double acc[2] = {0.0, 0.0};                                // sum w^2, sum x^2
   auto add = [&](float wi, float gi) {
     const double dw = (double)wi, dx = (double)(scale * opt_grad(gi, wd, wi));
-    aw += dw * dw;
-    ax += dx * dx;
+    acc[0] += dw * dw;
+    acc[1] += dx * dx;
   };
   for (int i = threadIdx.x; i < sp.head; i += kT) add(w[c.lo + i], g[c.lo + i]);
   const float4* w4 = reinterpret_cast<const float4*>(w + c.lo + sp.head);
@@ -71,7 +61,7 @@ trust_norms_sgd_kernel(const float* __restrict__ w, const float* __restrict__ g,
     add(wa.x, ga.x); add(wa.y, ga.y); add(wa.z, ga.z); add(wa.w, ga.w);
   }
   for (int j = sp.head + 4 * sp.n4 + threadIdx.x; j < c.len; j += kT) add(w[c.lo + j], g[c.lo + j]);
-  block_sum2(aw, ax, partials + 2 * (long long)blockIdx.x);
+  store_sums(acc, partials);
 }
 
 // adam: the moments are UPDATED here (AdamRule::Ready::moments, as mbx_adam_ema_step does), u formed from them by the rule's own
@@ -87,12 +77,12 @@ trust_moments_adam_kernel(const float* __restrict__ w, const float* __restrict__
   const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                      reinterpret_cast<uintptr_t>(v)) & 15) == 0;
   const Split sp = split_of(c, vec);
-  double aw = 0.0, au = 0.0;
+  double acc[2] = {0.0, 0.0};                                // sum w^2, sum u^2
   auto one = [&](float wi, float gi, float& mi, float& vi) {
     step.moments(scale * opt_grad(gi, wd, wi), mi, vi);
     const double dw = (double)wi, du = (double)step.update(wi, mi, vi);
-    aw += dw * dw;
-    au += du * du;
+    acc[0] += dw * dw;
+    acc[1] += du * du;
   };
   auto scalar = [&](long long e) {
     float mi = m[e], vi = v[e];
@@ -114,7 +104,7 @@ trust_moments_adam_kernel(const float* __restrict__ w, const float* __restrict__
     v4[i] = vv;
   }
   for (int j = sp.head + 4 * sp.n4 + threadIdx.x; j < c.len; j += kT) scalar(c.lo + j);
-  block_sum2(aw, au, partials + 2 * (long long)blockIdx.x);
+  store_sums(acc, partials);
 }
 
 // One wavefront per variable: lane l sums the slots of chunks first + l, first + l + 64, ... in that order, then the butterfly.
@@ -143,9 +133,8 @@ trust_ratios_kernel(const double* __restrict__ partials, const Var* __restrict__
   ratio[var] = r;
 }
 
-// opt_ema_kernel's surroundings (the gate, the EMA from the weight before the step, the regulariser sum, frozen ranges, the bf16
-// refresh) around Rule::trust, one workgroup per chunk, the variable's ratio loaded once per workgroup.  s0 / s1: the rule's
-// slots; adam only reads them (kTrustWritesSlots) and does not read g (kTrustReadsG).
+// OptBody's surroundings around Rule::trust, one workgroup per chunk, the variable's ratio loaded once per workgroup.  s0 / s1:
+// the rule's slots; adam only reads them (kTrustWritesSlots) and does not read g (kTrustReadsG).
 template <class Rule>
 __global__ void __launch_bounds__(kT)
 trust_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
@@ -153,71 +142,21 @@ trust_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __
                    float* __restrict__ reg_loss, const float* __restrict__ ctl, int clipped, const Chunk* __restrict__ chunks,
                    const float* __restrict__ ratio, const Rule rule) {
   if (gated(ctl)) return;
-  constexpr bool kA = Rule::kSlots >= 1, kB = Rule::kSlots >= 2, kG = Rule::kTrustReadsG, kWr = Rule::kTrustWritesSlots;
+  constexpr bool kG = Rule::kTrustReadsG;
   const float scale = clipped ? ctl[2] : 1.f;
   const auto step = rule.ready();
   const Chunk c = chunks[blockIdx.x];
   const float r = ratio[c.var];
-  float sq = 0.f;
-  auto one = [&](float wi, const float gi_, float& ai, float& bi, float& emai) -> float {
-    sq = fmaf(wi, wi, sq);
-    if (ema) emai = fmaf(-(1.0f - ema_decay), emai - wi, emai);       // emai - (1 - ema_decay) * (emai - wi)
-    if (trainable) wi = step.trust(wi, kG ? scale * opt_grad(gi_, wd, wi) : 0.f, ai, bi, r);
-    return wi;
+  auto new_w = [&](auto, float wi, float gi, float& ai, float& bi) -> float {
+    return step.trust(wi, kG ? scale * opt_grad(gi, wd, wi) : 0.f, ai, bi, r);
   };
-  const bool vec = ((reinterpret_cast<uintptr_t>(w) | (kG ? reinterpret_cast<uintptr_t>(g) : 0) |
-                     (kA ? reinterpret_cast<uintptr_t>(s0) : 0) | (kB ? reinterpret_cast<uintptr_t>(s1) : 0) |
-                     reinterpret_cast<uintptr_t>(ema)) & 15) == 0 && (reinterpret_cast<uintptr_t>(wb) & 7) == 0;
-  const Split sp = split_of(c, vec);
-  auto scalar = [&](long long e) {
-    float ai = 0.f, bi = 0.f, gi = 0.f, emai = ema ? ema[e] : 0.f;
-    if (trainable) {
-      if constexpr (kG) gi = g[e];
-      if constexpr (kA) ai = s0[e];
-      if constexpr (kB) bi = s1[e];
-    }
-    const float wi = one(w[e], gi, ai, bi, emai);
-    if (ema) ema[e] = emai;
-    if (trainable) {
-      if constexpr (kA && kWr) s0[e] = ai;
-      if constexpr (kB && kWr) s1[e] = bi;
-      w[e] = wi;
-    }
-    if (wb) wb[e] = (unsigned short)f2bf(wi);
-  };
-  for (int i = threadIdx.x; i < sp.head; i += kT) scalar(c.lo + i);
+  OptBody<Rule, kG, Rule::kTrustWritesSlots> body{w, g, s0, s1, ema, wb, ema_decay, trainable, 0.f};
+  const Split sp = split_of(c, body.aligned());
+  for (int i = threadIdx.x; i < sp.head; i += kT) body.one(c.lo + i, new_w);
   const long long b = c.lo + sp.head;
-  for (int i = threadIdx.x; i < sp.n4; i += kT) {
-    float4 wv = reinterpret_cast<const float4*>(w + b)[i];
-    float4 ev = ema ? reinterpret_cast<const float4*>(ema + b)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), av = gv, bv = gv;
-    if (trainable) {
-      if constexpr (kG) gv = reinterpret_cast<const float4*>(g + b)[i];
-      if constexpr (kA) av = reinterpret_cast<const float4*>(s0 + b)[i];
-      if constexpr (kB) bv = reinterpret_cast<const float4*>(s1 + b)[i];
-    }
-    wv.x = one(wv.x, gv.x, av.x, bv.x, ev.x); wv.y = one(wv.y, gv.y, av.y, bv.y, ev.y);
-    wv.z = one(wv.z, gv.z, av.z, bv.z, ev.z); wv.w = one(wv.w, gv.w, av.w, bv.w, ev.w);
-    if (ema) reinterpret_cast<float4*>(ema + b)[i] = ev;
-    if (trainable) {
-      if constexpr (kA && kWr) reinterpret_cast<float4*>(s0 + b)[i] = av;
-      if constexpr (kB && kWr) reinterpret_cast<float4*>(s1 + b)[i] = bv;
-      reinterpret_cast<float4*>(w + b)[i] = wv;
-    }
-    if (wb) reinterpret_cast<uint2*>(wb + b)[i] = make_uint2(pack2bf(wv.x, wv.y), pack2bf(wv.z, wv.w));
-  }
-  for (int j = sp.head + 4 * sp.n4 + threadIdx.x; j < c.len; j += kT) scalar(c.lo + j);
-  if (reg_loss && wd != 0.f) {
-    sq = wave_sum(sq);
-    __shared__ float red[kT / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int i = 0; i < kT / 64; ++i) t += red[i];
-      atomicAdd(reg_loss, 0.5f * wd * t);
-    }
-  }
+  for (int i = threadIdx.x; i < sp.n4; i += kT) body.four(b + 4 * i, new_w);
+  for (int j = sp.head + 4 * sp.n4 + threadIdx.x; j < c.len; j += kT) body.one(c.lo + j, new_w);
+  reg_finish(body.sq, wd, reg_loss);
 }
 
 template <class Rule>

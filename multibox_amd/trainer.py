@@ -269,18 +269,15 @@ class Trainer:
     def _trust_range_step(self, plan, lo, hi, lr, d, gate, clipped, s):
         """One trainable filter range under layerwise_trust: the norm pass (adam: it also updates the moments), the ratios,
         the apply pass -- in the place of _range_step's one launch.  No allocation, no host synchronisation."""
-        net, l = self.net, _lib.lib()
+        l = _lib.lib()
         n, nc = hi - lo, plan["n_chunks"]
-        P = lambda t_, el=4: None if t_ is None else t_.data_ptr() + el * lo
-        w, g, mom, ms, ema, wb = P(net.W), P(net.Wg), P(self.Wmom), P(self.Wms), P(self.Wema), P(net.Wb, 2)
+        w, g, ms, mom, ema, wb, _, reg = self._range_ptrs("W", lo)
         chunks, part, ratio = plan["chunks"].data_ptr(), plan["partials"].data_ptr(), plan["ratio"].data_ptr()
-        reg, c = net.reg_loss.data_ptr(), int(clipped)
+        c = int(clipped)
         if self.optimizer == "sgd":
             _lib.check(l.mbx_trust_norms_sgd(w, g, chunks, nc, self.wd_l2, part, gate, c, s), "trust_norms_sgd")
         else:
-            calls = self.global_step + self._opt_step_offset + self._skipped_seen       # (as _range_step)
-            assert calls >= 0, "optimizer step count out of step with global_step (%d, offset %d)" % (self.global_step, self._opt_step_offset)
-            sk = self.skipped_steps.data_ptr()
+            calls, sk = self._adam_calls(), self.skipped_steps.data_ptr()
             _lib.check(l.mbx_trust_moments_adam(w, g, mom, ms, chunks, nc, self.adam_beta1, self.adam_beta2, self.adam_eps, self.wd_l2,
                                                 self.wd_decoupled, calls, sk, part, gate, c, s), "trust_moments_adam")
         _lib.check(l.mbx_trust_ratios(part, plan["vars"].data_ptr(), plan["n_vars"], self.trust_coeff, ratio, gate, s), "trust_ratios")
@@ -665,33 +662,45 @@ class Trainer:
         """Steps the optimiser has applied on its present slots, as of the last fold of skipped steps."""
         return self.global_step + self._opt_step_offset
 
+    def _range_ptrs(self, buf, lo):
+        """(w, g, ms, mom, ema, wb, wd, reg) of the range of buffer `buf` ("W" or "Bt") that starts at element lo: device
+        addresses (None for a slot the rule does not keep), then what only filters carry -- the bf16 copy, the L2
+        coefficient and the regulariser sum (betas: None, 0.0, None)."""
+        net = self.net
+        P = lambda t_, el=4: None if t_ is None else t_.data_ptr() + el * lo
+        if buf == "W":
+            return P(net.W), P(net.Wg), P(self.Wms), P(self.Wmom), P(self.Wema), P(net.Wb, 2), self.wd_l2, net.reg_loss.data_ptr()
+        return P(net.Bt), P(net.Btg), P(self.Btms), P(self.Btmom), P(self.Btema), None, 0.0, None
+
+    def _adam_calls(self):
+        """Adam's `calls`: launches so far on these slots, skipped ones included -- the kernel takes the device's count of
+        those off again (never below the device's count of skipped steps: every skip was a launch, and both restores set
+        the offset)."""
+        calls = self.global_step + self._opt_step_offset + self._skipped_seen
+        assert calls >= 0, "optimizer step count out of step with global_step (%d, offset %d)" % (self.global_step, self._opt_step_offset)
+        return calls
+
     def _range_step(self, buf, lo, hi, on, lr, d, gate, clipped, s):
         """The optimiser launch of one range of self.opt_ranges under the chosen rule.  gate: the step control block, or the
         clip block with clipped = True.  Filters carry the L2 coefficient, the regulariser sum, the bf16 refresh and (adamw)
         the decoupled decay; betas none of them."""
-        net, l = self.net, _lib.lib()
+        l = _lib.lib()
         n = hi - lo
         if n <= 0:
             return
-        P = lambda t_, el=4: None if t_ is None else t_.data_ptr() + el * lo
         filt = buf == "W"
-        w, g, ms, mom, ema = (net.W, net.Wg, self.Wms, self.Wmom, self.Wema) if filt else (net.Bt, net.Btg, self.Btms, self.Btmom, self.Btema)
-        wb, wd, reg = (P(net.Wb, 2), self.wd_l2, net.reg_loss.data_ptr()) if filt else (None, 0.0, None)
+        w, g, ms, mom, ema, wb, wd, reg = self._range_ptrs(buf, lo)
         what = "%s %s%s" % (self.optimizer, "W" if filt else "beta", " (clipped)" if clipped else "")
         if self.optimizer == "rmsprop":
             entry = l.mbx_rmsprop_ema_step_clipped if clipped else l.mbx_rmsprop_ema_step
-            st = entry(P(w), P(g), P(ms), P(mom), P(ema), wb, n, lr, self.rms_decay, self.momentum, self.eps, wd, d, on, reg, gate, s)
+            st = entry(w, g, ms, mom, ema, wb, n, lr, self.rms_decay, self.momentum, self.eps, wd, d, on, reg, gate, s)
         elif self.optimizer == "sgd":
-            st = l.mbx_sgd_ema_step(P(w), P(g), P(mom), P(ema), wb, n, lr, self.sgd_momentum, int(self.sgd_nesterov), wd, d, on, reg,
+            st = l.mbx_sgd_ema_step(w, g, mom, ema, wb, n, lr, self.sgd_momentum, int(self.sgd_nesterov), wd, d, on, reg,
                                     gate, int(clipped), s)
         else:
-            # launches so far on these slots, skipped ones included: the kernel takes the device's count of those off again
-            # (never below the device's count of skipped steps: every skip was a launch, and both restores set the offset)
-            calls = self.global_step + self._opt_step_offset + self._skipped_seen
-            assert calls >= 0, "optimizer step count out of step with global_step (%d, offset %d)" % (self.global_step, self._opt_step_offset)
-            st = l.mbx_adam_ema_step(P(w), P(g), P(mom), P(ms), P(ema), wb, n, lr, self.adam_beta1, self.adam_beta2, self.adam_eps, wd,
-                                     self.wd_decoupled if filt else 0.0, calls, self.skipped_steps.data_ptr(), d, on, reg, gate,
-                                     int(clipped), s)
+            st = l.mbx_adam_ema_step(w, g, mom, ms, ema, wb, n, lr, self.adam_beta1, self.adam_beta2, self.adam_eps, wd,
+                                     self.wd_decoupled if filt else 0.0, self._adam_calls(), self.skipped_steps.data_ptr(), d, on, reg,
+                                     gate, int(clipped), s)
         _lib.check(st, what)
 
     def _optimizer(self):
@@ -704,37 +713,26 @@ class Trainer:
         d = min(self.ema_decay, (1.0 + t) / (10.0 + t))        # ExponentialMovingAverage(num_updates=global_step)
         self.lr = lr
         # (net.reg_loss was cleared by the step's mbx_step_begin launch: Net.zero_grads)
-        ctl = net.step_ctl.data_ptr()                  # non-zero -> every launch below is a no-op (poisoned step / stop request)
+        gate = net.step_ctl                            # non-zero -> every launch below is a no-op (poisoned step / stop request)
         if self.clip_norm is not None:
-            return self._optimizer_clipped(lr, d, s)
-        self._ranges_step(lr, d, ctl, False, s)
+            # clip_gradient_norm: the squared norm of every trainable range, then the clip block; the launches below go through
+            # the clipped entry points with the clip block as their gate (frozen ranges too: they skip together).  No
+            # allocation, no host synchronisation; every rank computes the same block from the reduced gradients.
+            l, slot = _lib.lib(), 0
+            for (buf, lo, hi, on), k in zip(self.opt_ranges, self._clip_slots):
+                if not k:
+                    continue
+                w, g, _, _, _, _, wd, _ = self._range_ptrs(buf, lo)      # (betas, and filters under adamw: no coupled L2 term, the norm is that of g alone)
+                _lib.check(l.mbx_grad_sqnorm(g, w if wd else None, hi - lo, wd, self._clip_partials.data_ptr() + 8 * slot, s),
+                           "grad_sqnorm " + ("W" if buf == "W" else "beta"))
+                slot += k
+            _lib.check(l.mbx_clip_finalize(self._clip_partials.data_ptr(), max(1, slot), self.clip_norm, net.step_ctl.data_ptr(),
+                                           self._clip_block.data_ptr(), self._clip_counts.data_ptr(), s), "clip_finalize")
+            gate = self._clip_block
+        self._ranges_step(lr, d, gate.data_ptr(), self.clip_norm is not None, s)
         # moving statistics <- this step's batch statistics, and their EMA shadows (train.py:257) from the new values: one gated launch
         assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
-        net.apply_moving_update(net.step_ctl, self.skipped_steps, self.MMema, self.MVema, d)
-        net.prepare_filters()
-
-    def _optimizer_clipped(self, lr, d, s):
-        """The optimiser phase under clip_gradient_norm: the squared norm of every trainable range, the clip block, then
-        _optimizer's launches through the clipped entry point with the clip block as their gate (frozen ranges too: they
-        skip together).  No allocation, no host synchronisation; every rank computes the same block from the reduced
-        gradients."""
-        net, l = self.net, _lib.lib()
-        P = lambda t_, off=0: None if t_ is None else t_.data_ptr() + 4 * off
-        slot = 0
-        for (buf, lo, hi, on), k in zip(self.opt_ranges, self._clip_slots):
-            if not k:
-                continue
-            part = self._clip_partials.data_ptr() + 8 * slot
-            if buf == "W":                             # (adamw: no coupled L2 term, the norm is that of g alone)
-                _lib.check(l.mbx_grad_sqnorm(P(net.Wg, lo), P(net.W, lo) if self.wd_l2 else None, hi - lo, self.wd_l2, part, s), "grad_sqnorm W")
-            else:
-                _lib.check(l.mbx_grad_sqnorm(P(net.Btg, lo), None, hi - lo, 0.0, part, s), "grad_sqnorm beta")
-            slot += k
-        _lib.check(l.mbx_clip_finalize(self._clip_partials.data_ptr(), max(1, slot), self.clip_norm, net.step_ctl.data_ptr(),
-                                       self._clip_block.data_ptr(), self._clip_counts.data_ptr(), s), "clip_finalize")
-        self._ranges_step(lr, d, self._clip_block.data_ptr(), True, s)
-        assert self.bt_lo == (net.head_bt_start if net.fine_tune else 0)
-        net.apply_moving_update(self._clip_block, self.skipped_steps, self.MMema, self.MVema, d)
+        net.apply_moving_update(gate, self.skipped_steps, self.MMema, self.MVema, d)
         net.prepare_filters()
 
     def grad_norm(self):

@@ -79,17 +79,17 @@ class State(GO.State):
         _lib.check(st, rule + " norms")
         _lib.check(l.mbx_trust_ratios(p(pl.partials), p(pl.vars), pl.nv, coeff, p(pl.ratio), p(ctl), GC.S()), "ratios")
 
-    def apply(self, l, rule, kw, wd=WD, ctl=None, clipped=0, calls=0, lr=HY["lr"]):
+    def apply(self, l, rule, kw, wd=WD, ctl=None, clipped=0, calls=0, lr=HY["lr"], trainable=1):
         from multibox_amd import _lib
         p = lambda t: None if t is None else t.data_ptr()
         pl = self.plan
         tail = (p(pl.chunks), pl.nc, p(pl.ratio), GC.S())
         if rule == "sgd":
             st = l.mbx_sgd_ema_step_trust(p(self.w), p(self.g), p(self.a) if kw["momentum"] else None, p(self.ema), p(self.wb), self.n, lr,
-                                          kw["momentum"], int(kw["nesterov"]), wd, HY["d"], 1, p(self.reg), p(ctl), clipped, *tail)
+                                          kw["momentum"], int(kw["nesterov"]), wd, HY["d"], trainable, p(self.reg), p(ctl), clipped, *tail)
         else:
             st = l.mbx_adam_ema_step_trust(p(self.w), p(self.g), p(self.a), p(self.b), p(self.ema), p(self.wb), self.n, lr, ADAM["beta1"],
-                                           ADAM["beta2"], ADAM["eps"], wd, kw["wd_decoupled"], calls, None, HY["d"], 1, p(self.reg),
+                                           ADAM["beta2"], ADAM["eps"], wd, kw["wd_decoupled"], calls, None, HY["d"], trainable, p(self.reg),
                                            p(ctl), clipped, *tail)
         _lib.check(st, rule + " apply")
 

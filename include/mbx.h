@@ -293,6 +293,58 @@ int mbx_loss_fwd_bwd_loc(const float* decoded /*[B,P,4]*/, const float* conf_in 
                          int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
                          void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
+/* mbx_loss_fwd_bwd_loc with an IOU-AWARE CONFIDENCE TARGET (optional, not in the reference, off unless the caller asks): a
+ * positive trains its confidence towards q, the IoU of its prediction with its box, not towards 1 -- the Quality Focal Loss
+ * (Li et al. 2020, "Generalized Focal Loss") or the Varifocal Loss (Zhang et al. 2021, "VarifocalNet").  The one entry for
+ * every combination of location term, mining and confidence term.  Every argument but `quality` and `q_stats` is
+ * mbx_loss_fwd_bwd_loc's, same order and meaning.
+ * MBX_QUALITY_NONE: loss2, d_raw_locs, d_logits and n_neg are byte-identical to mbx_loss_fwd_bwd_loc on the same remaining
+ * arguments (the same launches); q_stats must be NULL.
+ * MBX_QUALITY_QFL / MBX_QUALITY_VFL.  Per prior, s, c, w and ds are mbx_loss_fwd_bwd_focal's float32 quantities:
+ *   s = sigmoid(conf_in) when conf_is_logit, else conf_in;   c = s + 1e-10f;   w = (1 - c) + 1e-10f
+ *   ds = s (1 - s) when conf_is_logit, else 1
+ * A negative keeps mbx_loss_fwd_bwd_focal's float32 lines: counted as there (every negative when neg_per_pos == 0, else the
+ * selection of mbx_loss_fwd_bwd_mined -- the term is increasing in c, so the highest score is still the highest loss), its
+ * term is -w_neg * c^gamma * log w, an unselected one adds nothing and gets +0.0f.
+ * A positive (match[b,p] = m >= 0) is computed in float64 from the widened float32 values, l = decoded[b,p], g = gt[b,m]:
+ *   q = IoU = I / (U + 1e-7) exactly as mbx_loss_fwd_bwd_loc's IoU family defines it: the prediction put in order first, the
+ *     ground truth as given.  q is a CONSTANT in the gradient -- a target; nothing flows to d_raw_locs through it.
+ *   t = q log c + (1 - q) log w                      dt/ds = q / c - (1 - q) / w
+ *   QFL: M = |q - s|^gamma;  dM/ds = -gamma |q - s|^(gamma-1) sgn(q - s), exactly 0 where q == s (the kink passes no gradient,
+ *        as max(0, .) in the location terms); with gamma == 0 M is the constant 1 and the dM term is left out.
+ *   VFL: M = q;  dM/ds = 0.
+ *   term L = -w_pos M t      dL/ds = -w_pos (dM/ds t + M dt/ds)      d_logits = (float)(dL/ds * ds * grad_scale), one rounding
+ *   L goes into the image's confidence sum in double.  loss2[1] is the sum of all terms; nothing is normalised by the number
+ *   of positives.  The papers' settings are w_pos = 1 with w_neg = 1 (QFL) or 0.75 (VFL), gamma = 2.
+ * gamma is in [0, 10] as for the focal loss, and under QFL 0 or >= 1: for 0 < gamma < 1 the factor |q - s|^(gamma-1) is
+ * unbounded as s -> q and a float32 gradient can overflow, so that range is refused.  At gamma == 1 the QFL gradient jumps
+ * at q == s.  With c, w >= 1e-10 every term and gradient is finite for finite inputs: s exactly 0 or 1, q == 0 (disjoint
+ * boxes) and degenerate predictions (inverted, zero-width, zero-area) included.
+ * A VFL positive with q == 0 contributes neither loss nor gradient (the paper's behaviour; common in the first steps of
+ * training).  A QFL positive with q == 0 is pushed down like a negative.
+ * The location side (loss2[0], d_raw_locs), n_neg and the d_logits of every negative are byte-identical to
+ * mbx_loss_fwd_bwd_loc with the same loc_type, loc_beta, gamma, w_neg, neg_per_pos and min_neg.
+ * q_stats (may be NULL): q_stats[b] = {the sum of q over the positives of image b, their number}, both doubles, summed in a
+ * fixed lane / wavefront order.  An image's outputs depend on its own row only, and the same input gives the same bytes on
+ * every call (no floating-point atomics).  Any P.
+ * An unknown quality, 0 < gamma < 1 with MBX_QUALITY_QFL, a q_stats with MBX_QUALITY_NONE, or anything mbx_loss_fwd_bwd_loc
+ * rejects: MBX_ERR_INVALID_ARG; workspace_bytes < mbx_loss_quality_workspace_bytes(B, P): MBX_ERR_WORKSPACE (a bad argument
+ * is reported first); nothing is launched or written either way.  Two launches on `stream`, one workgroup per image,
+ * graph-capturable.
+ * What either target does to AP on real data is NOT measured here: no trained model or dataset is at hand.             */
+enum { MBX_QUALITY_NONE = 0, MBX_QUALITY_QFL = 1, MBX_QUALITY_VFL = 2 };
+size_t mbx_loss_quality_workspace_bytes(int B, int P);
+int mbx_loss_fwd_bwd_quality(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B,P]*/,
+                             int conf_is_logit, const float* gt /*[B,G,4]*/,
+                             const int32_t* match /*[B,P]*/, float alpha, float grad_scale, int B, int P,
+                             int G, float* loss2 /*[2]*/,
+                             float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
+                             int loc_type /*MBX_LOC_*/, float loc_beta /*MBX_LOC_SMOOTH_L1 only*/,
+                             int quality /*MBX_QUALITY_*/, float gamma, float w_pos, float w_neg,
+                             int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
+                             double* q_stats /*[B,2] or NULL*/,
+                             void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
 /* ------------------------------------------------- detect post-processing (A9-A12)
  * Replaces the per-patch numpy loop detect.py:408-436: decode + clip [0,1]
  * (412-413), filter_proposals (74-104, strict inequalities), sort by confidence

@@ -46,6 +46,8 @@ _SIGS = {
     "mbx_loss_fwd_bwd_focal": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, F, F, F, I, I, P, P, SZ, P]),
     "mbx_loss_loc_workspace_bytes": (SZ, [I, I]),
     "mbx_loss_fwd_bwd_loc": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, I, F, F, F, F, I, I, P, P, SZ, P]),
+    "mbx_loss_quality_workspace_bytes": (SZ, [I, I]),
+    "mbx_loss_fwd_bwd_quality": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, I, F, I, F, F, F, I, I, P, P, P, SZ, P]),
     "mbx_decode_filter_topk": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "mbx_nms": (I, [P, P, P, P, I, I, C.c_double, P]),
     "mbx_merge_detections": (I, [P, P, P, P, I, I, I, C.c_double, P, P, P, P, P, P]),

@@ -150,6 +150,48 @@ def loc_loss(cfg):
     return kind, float(beta)
 
 
+QUALITY_TARGETS = ("qfl", "varifocal")                       # MBX_QUALITY_QFL = 1, MBX_QUALITY_VFL = 2 (include/mbx.h)
+
+
+def quality_loss(cfg):
+    """An IoU-aware confidence target (mbx_loss_fwd_bwd_quality; not in the reference, so off when absent): None, or a dict
+    of Trainer keyword arguments.
+      LOSS_QUALITY_TARGET      qfl (the Quality Focal Loss of Generalized Focal Loss, Li et al. 2020) or varifocal (the
+        Varifocal Loss of VarifocalNet, Zhang et al. 2021); absent or null = off.  A positive trains its confidence towards
+        the IoU of its prediction with its box; the scores then estimate localisation quality as well as objectness.
+      LOSS_QUALITY_GAMMA       a number in [0, 10], under qfl 0 or >= 1 (|q - s|^(gamma-1) is unbounded below 1); default 2.0;
+        only with the target.
+      LOSS_QUALITY_NEG_WEIGHT  finite and > 0 as a float32; default 1.0 under qfl and 0.75 under varifocal, the papers'
+        settings; only with the target.
+    LOSS_FOCAL_GAMMA or LOSS_FOCAL_ALPHA beside the target raises ValueError naming both keys: each decides the confidence
+    term.  A bool, a string where a number is expected, a list, a NaN, a value out of range or a dependent key without the
+    target raises ValueError naming the key.  Composes with LOSS_LOC_TYPE, LOSS_NEG_PER_POS and the matching keys.  Host code
+    only."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    target, gamma, w_neg = cfg.get("LOSS_QUALITY_TARGET"), cfg.get("LOSS_QUALITY_GAMMA"), cfg.get("LOSS_QUALITY_NEG_WEIGHT")
+    if target is None:
+        for key, v in (("LOSS_QUALITY_GAMMA", gamma), ("LOSS_QUALITY_NEG_WEIGHT", w_neg)):
+            if v is not None:
+                raise ValueError("%s is given without LOSS_QUALITY_TARGET" % key)
+        return None
+    if not (isinstance(target, str) and target in QUALITY_TARGETS):
+        raise ValueError("LOSS_QUALITY_TARGET must be one of %s, got %r" % (", ".join(QUALITY_TARGETS), target))
+    for key in ("LOSS_FOCAL_GAMMA", "LOSS_FOCAL_ALPHA"):
+        if cfg.get(key) is not None:
+            raise ValueError("LOSS_QUALITY_TARGET and %s are both given: each decides the confidence term" % key)
+    if gamma is None:
+        gamma = 2.0
+    elif not (number(gamma) and 0 <= gamma <= 10):
+        raise ValueError("LOSS_QUALITY_GAMMA must be a number in [0, 10], got %r" % (gamma,))
+    elif target == "qfl" and 0 < gamma < 1:
+        raise ValueError("LOSS_QUALITY_GAMMA must be 0 or >= 1 under LOSS_QUALITY_TARGET qfl, got %r" % (gamma,))
+    if w_neg is None:
+        w_neg = 1.0 if target == "qfl" else 0.75
+    elif not (number(w_neg) and 0 < ctypes.c_float(w_neg).value < float("inf")):
+        raise ValueError("LOSS_QUALITY_NEG_WEIGHT must be a finite number > 0 as a float32, got %r" % (w_neg,))
+    return {"quality_target": target, "quality_gamma": float(gamma), "quality_neg_weight": float(w_neg)}
+
+
 def grad_clip(cfg):
     """Global-norm gradient clipping and the non-finite-step guard (mbx_grad_sqnorm / mbx_clip_finalize /
     mbx_rmsprop_ema_step_clipped; not in the reference, so off when absent): None, or CLIP_GRADIENT_NORM as a float > 0

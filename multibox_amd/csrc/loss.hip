@@ -633,6 +633,49 @@ __device__ __forceinline__ double loc_term(int loc_type, double beta, const floa
   return L;
 }
 
+// ------------------------------------------------------- IoU-aware confidence target
+// The positive side of mbx_loss_fwd_bwd_quality (mbx.h has the definition), in float64 from the widened float32 values.
+// q is the IoU of loc_term's IoU family, from the same loc_axis on the same inputs: the prediction put in order, the ground
+// truth as given, I / (U + 1e-7).
+__device__ __forceinline__ double quality_iou(const float4 lf, const float4 gf) {
+  const LocAxis X = loc_axis((double)lf.x, (double)lf.z, (double)gf.x, (double)gf.z);
+  const LocAxis Y = loc_axis((double)lf.y, (double)lf.w, (double)gf.y, (double)gf.w);
+  const double inter = X.ov * Y.ov;
+  const double uni = X.ext * Y.ext + X.gext * Y.gext - inter;
+  return inter / (uni + 1e-7);
+}
+
+// Returns the term L = -w_pos M t, t = q log c + (1 - q) log w; dLds = -w_pos (dM/ds t + M dt/ds), q a constant.
+//   QFL: M = |q - s|^gamma; dM/ds = -gamma |q - s|^(gamma-1) sgn(q - s), taken as M / |q - s| (one pow), and exactly 0 at
+//        q == s; with gamma == 0 M is the constant 1 and the dM term is left out.  gamma is 0 or >= 1 (the entry checks);
+//        gamma == 2, the papers' exponent and the host's default, is (q - s)^2 and -2 (q - s): no pow, no quotient (the pow and
+//        the quotient are 2.2 of the 4.8 us QFL adds to a call at P = 646, tools/loss_quality_bench.py).
+//   VFL: M = q, no dM term.
+// `quality` is the same for the whole launch: the switch is wavefront-uniform.  c, w >= 1e-10: both logs are finite.
+__device__ __forceinline__ double quality_positive(int quality, double q, float sf, float cf, float wf, float gamma,
+                                                   float w_pos, double& dLds) {
+  const double s = (double)sf, c = (double)cf, w = (double)wf, wp = (double)w_pos;
+  const double t = q * log(c) + (1.0 - q) * log(w);
+  const double dt = q / c - (1.0 - q) / w;
+  if (quality == MBX_QUALITY_VFL || gamma == 0.0f) {
+    const double M = quality == MBX_QUALITY_VFL ? q : 1.0;
+    dLds = -wp * (M * dt);
+    return -wp * M * t;
+  }
+  const double diff = q - s;
+  double M, dM;
+  if (gamma == 2.0f) {                                       // the papers' exponent: (q - s)^2 and -2 (q - s), no pow, no quotient
+    M = diff * diff;
+    dM = -2.0 * diff;
+  } else {
+    const double a = fabs(diff);
+    M = pow(a, (double)gamma);
+    dM = diff == 0.0 ? 0.0 : (diff > 0.0 ? -(double)gamma : (double)gamma) * (M / a);
+  }
+  dLds = -wp * (dM * t + M * dt);
+  return -wp * M * t;
+}
+
 // ------------------------------------------------- loss with hard-negative mining
 // Composite key of a negative: the order-preserving image of its input float (score_order_key) above the INVERTED index
 // P-1-p, so that unsigned order = (score descending, p ascending) and no two candidates are equal.
@@ -730,20 +773,29 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
 //   LOC_ANY: the location term of a positive is the one `loc_type` names (loc_term above, float64; MBX_LOC_L2 takes the
 //     float32 lines of the other kernels, so that type gives their bytes).  Without LOC_ANY it is L2 at compile time and
 //     loc_type and loc_beta are not read: the four kernels from before the choice keep their code.
-template <bool MINED, bool FOCAL, bool LOC_ANY>
+//   QUALITY (with FOCAL): a positive's confidence target is q, the IoU of its prediction with its box (quality_positive
+//     above, float64: two logs and at most one pow for the few lanes that hold a positive), and the image's sum of q and
+//     number of positives go to q_stats.  `quality` (MBX_QUALITY_QFL or _VFL) is the same for the whole launch, like
+//     loc_type.  The negatives run the float32 lines below unchanged: their d_logits are loss_loc_kernel's bytes.  q is
+//     taken from loc_axis here, not handed over by loc_term: the location lines stay what they are.  Without QUALITY
+//     `quality` and q_stats are not read and nothing of this is compiled in.
+template <bool MINED, bool FOCAL, bool LOC_ANY, bool QUALITY>
 __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
                                           const float4* __restrict__ gt, const int* __restrict__ match, float alpha,
                                           float grad_scale, int P, int G, int loc_type, float loc_beta, float gamma,
                                           float w_pos, float w_neg, int neg_per_pos, int min_neg,
                                           double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
-                                          float* __restrict__ d_logits, int* __restrict__ n_neg) {
-  constexpr bool kCountPositives = FOCAL && !MINED;
+                                          float* __restrict__ d_logits, int* __restrict__ n_neg, int quality,
+                                          double* __restrict__ q_stats /*[B,2]*/) {
+  static_assert(!QUALITY || FOCAL, "the quality target replaces the focal positive term");
+  constexpr bool kNegFromPositives = FOCAL && !MINED;        // n_neg[b] = P - positives
+  constexpr bool kCountPositives = kNegFromPositives || QUALITY;
   const int b = blockIdx.x, tid = threadIdx.x;
   unsigned long long cut = 0ull;                             // no key is below 0: every negative counts
   if (MINED) cut = mined_select_cut(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg, b, n_neg);
   const bool modulated = FOCAL && gamma != 0.0f;
 
-  double loc_acc = 0.0, conf_acc = 0.0;
+  double loc_acc = 0.0, conf_acc = 0.0, q_acc = 0.0;
   int n_pos = 0;
   for (int p = tid; p < P; p += kThreads) {
     const size_t i = (size_t)b * P + p;
@@ -773,28 +825,39 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
           dl = make_float4((float)(a * dx1), (float)(a * dy1), (float)(a * dx2), (float)(a * dy2));
         }
         if (kCountPositives) ++n_pos;
+        if (QUALITY) {
+          const double iou = quality_iou(l, q);
+          double dLds;
+          conf_acc += quality_positive(quality, iou, s, c, w, gamma, w_pos, dLds);
+          q_acc += iou;
+          g = (float)(dLds * (double)ds * (double)grad_scale);                                // one rounding, at the store
+        }
       }
-      // The two sides are one expression with c and w exchanged, -wt * base^gamma * log(arg): one logf and one powf for
-      // a wavefront that holds positives and negatives, not one of each per side.
-      const float arg = pos ? c : w, base = pos ? w : c, wt = FOCAL ? (pos ? w_pos : w_neg) : 1.0f;
-      const float lg = logf(arg);                                                         // loss.py:101
-      const float pw = modulated ? powf(base, gamma) : 1.0f;
-      conf_acc -= (double)wt * ((double)pw * (double)lg);
-      float d = (ds * pw) / arg;
-      if (modulated) d = d - gamma * (pw / base) * lg * ds;               // lg <= 0: both terms are >= 0, no cancellation
-      d = wt * d;
-      g = (pos ? -d : d) * grad_scale;
+      if (!(QUALITY && pos)) {
+        // The two sides are one expression with c and w exchanged, -wt * base^gamma * log(arg): one logf and one powf for
+        // a wavefront that holds positives and negatives, not one of each per side.
+        const float arg = pos ? c : w, base = pos ? w : c, wt = FOCAL ? (pos ? w_pos : w_neg) : 1.0f;
+        const float lg = logf(arg);                                                         // loss.py:101
+        const float pw = modulated ? powf(base, gamma) : 1.0f;
+        conf_acc -= (double)wt * ((double)pw * (double)lg);
+        float d = (ds * pw) / arg;
+        if (modulated) d = d - gamma * (pw / base) * lg * ds;               // lg <= 0: both terms are >= 0, no cancellation
+        d = wt * d;
+        g = (pos ? -d : d) * grad_scale;
+      }
     }
     if (d_locs) d_locs[i] = dl;
     if (d_logits) d_logits[i] = g;
   }
   loc_acc = wave_sum(loc_acc);
   conf_acc = wave_sum(conf_acc);
-  __shared__ double red[kWaves][2];
+  if (QUALITY) q_acc = wave_sum(q_acc);
+  __shared__ double red[kWaves][QUALITY ? 3 : 2];
   __shared__ int pos_waves[kWaves];
   if (kCountPositives) n_pos = wave_sum(n_pos);
   if ((tid & 63) == 0) {
     red[tid >> 6][0] = loc_acc; red[tid >> 6][1] = conf_acc;
+    if (QUALITY) red[tid >> 6][QUALITY ? 2 : 0] = q_acc;
     if (kCountPositives) pos_waves[tid >> 6] = n_pos;
   }
   __syncthreads();
@@ -803,10 +866,15 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
     for (int w = 0; w < kWaves; ++w) { a += red[w][0]; c += red[w][1]; }
     partial[2 * b] = a;
     partial[2 * b + 1] = c;
-    if (kCountPositives && n_neg) {                          // every negative counts
-      int total = 0;
+    int total = 0;
+    if (kCountPositives)
       for (int w = 0; w < kWaves; ++w) total += pos_waves[w];
-      n_neg[b] = P - total;
+    if (kNegFromPositives && n_neg) n_neg[b] = P - total;    // every negative counts
+    if (QUALITY && q_stats) {                                // the wavefronts' sums in their fixed order: the same bytes every call
+      double qs = 0.0;
+      for (int w = 0; w < kWaves; ++w) qs += red[w][QUALITY ? 2 : 0];
+      q_stats[2 * b] = qs;
+      q_stats[2 * b + 1] = (double)total;
     }
   }
 }
@@ -816,8 +884,8 @@ loss_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits
             const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
             int P, int G, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
             float* __restrict__ d_logits) {
-  loss_body<false, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
-                                 1.0f, 0, 0, partial, d_locs, d_logits, nullptr);
+  loss_body<false, false, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
+                                 1.0f, 0, 0, partial, d_locs, d_logits, nullptr, MBX_QUALITY_NONE, nullptr);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -825,8 +893,8 @@ loss_mined_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
                   const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
                   int P, int G, int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/,
                   float4* __restrict__ d_locs, float* __restrict__ d_logits, int* __restrict__ n_neg) {
-  loss_body<true, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
-                                1.0f, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
+  loss_body<true, false, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, 0.0f, 1.0f,
+                                1.0f, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg, MBX_QUALITY_NONE, nullptr);
 }
 
 template <bool MINED>
@@ -836,8 +904,8 @@ loss_focal_kernel(const float4* __restrict__ decoded, const float* __restrict__ 
                   int P, int G, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
                   double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs, float* __restrict__ d_logits,
                   int* __restrict__ n_neg) {
-  loss_body<MINED, true, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, gamma, w_pos,
-                                w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
+  loss_body<MINED, true, false, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, MBX_LOC_L2, 0.0f, gamma, w_pos,
+                                w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg, MBX_QUALITY_NONE, nullptr);
 }
 
 // mbx_loss_fwd_bwd_loc: loss_focal_kernel<MINED> with the location term chosen at run time.
@@ -848,8 +916,20 @@ loss_loc_kernel(const float4* __restrict__ decoded, const float* __restrict__ lo
                 int P, int G, int loc_type, float loc_beta, float gamma, float w_pos, float w_neg, int neg_per_pos,
                 int min_neg, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
                 float* __restrict__ d_logits, int* __restrict__ n_neg) {
-  loss_body<MINED, true, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta, gamma, w_pos,
-                               w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg);
+  loss_body<MINED, true, true, false>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta, gamma, w_pos,
+                               w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg, MBX_QUALITY_NONE, nullptr);
+}
+
+// mbx_loss_fwd_bwd_quality under MBX_QUALITY_QFL / _VFL: loss_loc_kernel<MINED> with the IoU as the positives' target.
+template <bool MINED>
+__global__ void __launch_bounds__(kThreads)
+loss_quality_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                    const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                    int P, int G, int loc_type, float loc_beta, int quality, float gamma, float w_pos, float w_neg,
+                    int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
+                    float* __restrict__ d_logits, int* __restrict__ n_neg, double* __restrict__ q_stats /*[B,2]*/) {
+  loss_body<MINED, true, true, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta, gamma,
+                                     w_pos, w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg, quality, q_stats);
 }
 
 }  // namespace
@@ -965,18 +1045,19 @@ extern "C" size_t mbx_loss_workspace_bytes(int B) { return (size_t)(B > 0 ? B : 
 extern "C" size_t mbx_loss_mined_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 extern "C" size_t mbx_loss_focal_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 extern "C" size_t mbx_loss_loc_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+extern "C" size_t mbx_loss_quality_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 
-// What the four loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
+// What the five loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
 // the kernel of `kind`, then loss_final_kernel.  An entry checks its own arguments first; those and the ones here all
-// answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal and loc mine iff neg_per_pos != 0;
-// loc_type is MBX_LOC_L2 for every kind but kLoc.
-enum class LossKind { kPlain, kMined, kFocal, kLoc };
+// answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal, loc and quality mine iff
+// neg_per_pos != 0; loc_type is MBX_LOC_L2 for every kind but kLoc and kQuality; quality and q_stats are kQuality's.
+enum class LossKind { kPlain, kMined, kFocal, kLoc, kQuality };
 
 static int launch_loss(LossKind kind, const float* decoded, const float* logits, int conf_is_logit, const float* gt,
                        const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
                        float* d_raw_locs, float* d_logits, int loc_type, float loc_beta, float gamma, float w_pos,
                        float w_neg, int neg_per_pos, int min_neg, int32_t* n_neg, void* workspace, size_t workspace_bytes,
-                       mbx_stream_t stream) {
+                       mbx_stream_t stream, int quality = MBX_QUALITY_NONE, double* q_stats = nullptr) {
   if (!decoded || !logits || !gt || !match || !loss2 || B <= 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < mbx_loss_workspace_bytes(B)) return MBX_ERR_WORKSPACE;
   double* partial = reinterpret_cast<double*>(workspace);
@@ -1002,6 +1083,11 @@ static int launch_loss(LossKind kind, const float* decoded, const float* logits,
       hipLaunchKernelGGL(neg_per_pos ? loss_loc_kernel<true> : loss_loc_kernel<false>, dim3(B), dim3(kThreads), 0,
                          mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, loc_type, loc_beta,
                          gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg);
+      break;
+    case LossKind::kQuality:
+      hipLaunchKernelGGL(neg_per_pos ? loss_quality_kernel<true> : loss_quality_kernel<false>, dim3(B), dim3(kThreads), 0,
+                         mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, loc_type, loc_beta,
+                         quality, gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg, q_stats);
       break;
   }
   MBX_LAUNCH_CHECK();
@@ -1058,4 +1144,25 @@ extern "C" int mbx_loss_fwd_bwd_loc(const float* decoded, const float* logits, i
   return launch_loss(LossKind::kLoc, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
                      d_raw_locs, d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
                      workspace_bytes, stream);
+}
+
+extern "C" int mbx_loss_fwd_bwd_quality(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                        const int32_t* match, float alpha, float grad_scale, int B, int P, int G,
+                                        float* loss2, float* d_raw_locs, float* d_logits, int loc_type, float loc_beta,
+                                        int quality, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
+                                        int32_t* n_neg, double* q_stats, void* workspace, size_t workspace_bytes,
+                                        mbx_stream_t stream) {
+  if (quality < MBX_QUALITY_NONE || quality > MBX_QUALITY_VFL) return MBX_ERR_INVALID_ARG;
+  if (quality == MBX_QUALITY_NONE && q_stats) return MBX_ERR_INVALID_ARG;
+  if (quality == MBX_QUALITY_QFL && gamma > 0.0f && gamma < 1.0f) return MBX_ERR_INVALID_ARG;   // |q - s|^(gamma-1) is unbounded
+  if (quality == MBX_QUALITY_NONE)                           // the same launches: mbx_loss_fwd_bwd_loc's bytes
+    return mbx_loss_fwd_bwd_loc(decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2, d_raw_locs,
+                                d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
+                                workspace_bytes, stream);
+  if (loc_type < MBX_LOC_L2 || loc_type > MBX_LOC_CIOU) return MBX_ERR_INVALID_ARG;
+  if (loc_type == MBX_LOC_SMOOTH_L1 && !(loc_beta > 0.0f && !isinf(loc_beta))) return MBX_ERR_INVALID_ARG;   // a NaN fails
+  if (!focal_arguments_ok(gamma, w_pos, w_neg, neg_per_pos, min_neg)) return MBX_ERR_INVALID_ARG;
+  return launch_loss(LossKind::kQuality, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
+                     workspace_bytes, stream, quality, q_stats);
 }

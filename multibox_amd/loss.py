@@ -144,6 +144,32 @@ def _loc_arguments(loc_loss, loc_beta):
     return LOC_TYPES.index(loc_loss), float(loc_beta)
 
 
+QUALITY_TARGETS = ("qfl", "varifocal")                       # MBX_QUALITY_QFL = 1, MBX_QUALITY_VFL = 2 (include/mbx.h)
+QUALITY_NEG_WEIGHT_DEFAULT = {"qfl": 1.0, "varifocal": 0.75}  # the papers' settings
+
+
+def _quality_arguments(quality_target, quality_gamma, quality_neg_weight):
+    """None (off), or (quality, gamma, w_pos, w_neg) as mbx_loss_fwd_bwd_quality takes them.  Raises ValueError on a bad
+    value."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if quality_target is None:
+        for name, v in (("quality_gamma", quality_gamma), ("quality_neg_weight", quality_neg_weight)):
+            if v is not None:
+                raise ValueError("%s is given without quality_target" % name)
+        return None
+    if not (isinstance(quality_target, str) and quality_target in QUALITY_TARGETS):
+        raise ValueError("quality_target must be one of %s, got %r" % (", ".join(QUALITY_TARGETS), quality_target))
+    gamma = 2.0 if quality_gamma is None else quality_gamma
+    if not (number(gamma) and 0.0 <= gamma <= 10.0):
+        raise ValueError("quality_gamma must be a number in [0, 10], got %r" % (gamma,))
+    if quality_target == "qfl" and 0.0 < gamma < 1.0:
+        raise ValueError("quality_gamma must be 0 or >= 1 with quality_target 'qfl', got %r" % (gamma,))
+    w_neg = QUALITY_NEG_WEIGHT_DEFAULT[quality_target] if quality_neg_weight is None else quality_neg_weight
+    if not (number(w_neg) and 0.0 < ctypes.c_float(w_neg).value < float("inf")):
+        raise ValueError("quality_neg_weight must be a finite number > 0 (as a float32), got %r" % (w_neg,))
+    return QUALITY_TARGETS.index(quality_target) + 1, float(gamma), 1.0, float(w_neg)
+
+
 class MultiboxLoss:
     """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step).
 
@@ -176,13 +202,25 @@ class MultiboxLoss:
     combination with the three switches above; "l2" gives the reference's bytes through it).  loc_beta (a finite float > 0,
     default 0.1; only with "smooth_l1") is where smooth-L1 turns from quadratic to linear.  The match keeps the reference's
     L2-based cost.  location_loss_alpha's 1000 was sized for L2: with an IoU type, whose term is of order 1 per positive,
-    pass your own.  What any of these does to AP on real data is not measured here either."""
+    pass your own.  What any of these does to AP on real data is not measured here either.
+
+    quality_target ("qfl" or "varifocal"; None = off): an IoU-aware confidence target -- a positive trains its confidence
+    towards the IoU of its prediction with its box, by the Quality Focal Loss or the Varifocal Loss
+    (mbx_loss_fwd_bwd_quality, include/mbx.h, the one entry for every combination with loc_loss and neg_per_pos; w_pos = 1).
+    quality_gamma (a float in [0, 10], under "qfl" 0 or >= 1; default 2) is the exponent of both sides, quality_neg_weight
+    (finite and > 0; default 1 under "qfl", 0.75 under "varifocal") weighs the negatives; both only with the target.  Not
+    together with focal_gamma / focal_alpha: each decides the confidence term.  The sum of the positives' IoUs and their
+    number per image are left in ``q_stats`` ([B, 2] float64).  Scores trained this way estimate localisation quality as
+    well as objectness.  What that does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
                  min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
-                 atss_topk=None, prior_levels=None):
+                 atss_topk=None, prior_levels=None, quality_target=None, quality_gamma=None, quality_neg_weight=None):
         self.focal = _focal_arguments(focal_gamma, focal_alpha)
         self.loc = _loc_arguments(loc_loss, loc_beta)
+        self.quality = _quality_arguments(quality_target, quality_gamma, quality_neg_weight)
+        if self.quality is not None and self.focal is not None:
+            raise ValueError("quality_target and focal_gamma / focal_alpha are both given: each decides the confidence term")
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
         self.P = self.priors.shape[0]
         self.B, self.G, self.alpha = int(batch_size), int(max_num_bboxes), float(location_loss_alpha)
@@ -201,7 +239,13 @@ class MultiboxLoss:
             mining = (neg_per_pos, min_neg, self.n_neg.data_ptr())
         # the entry forward_backward calls, the arguments it has between the common ones and the workspace, its workspace
         l = _lib.lib()
-        if self.loc is not None:
+        self.q_stats = None
+        if self.quality is not None:
+            self.q_stats = torch.zeros((self.B, 2), dtype=torch.float64, device=device)
+            self.entry = "mbx_loss_fwd_bwd_quality"
+            self.entry_args = (self.loc or (0, 0.0)) + self.quality + mining + (self.q_stats.data_ptr(),)
+            ws_bytes = l.mbx_loss_quality_workspace_bytes(self.B, self.P)
+        elif self.loc is not None:
             self.entry, self.entry_args = "mbx_loss_fwd_bwd_loc", self.loc + (self.focal or (0.0, 1.0, 1.0)) + mining
             ws_bytes = l.mbx_loss_loc_workspace_bytes(self.B, self.P)
         elif self.focal is not None:

@@ -49,6 +49,7 @@ class Trainer:
                  rmsprop_momentum=0.0, rmsprop_epsilon=1.0, moving_average_decay=0.9999, use_graph=True,
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
                  match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
+                 quality_target=None, quality_gamma=None, quality_neg_weight=None,
                  clip_gradient_norm=None, optimizer="rmsprop", sgd_momentum=0.9, sgd_nesterov=False, adam_beta1=0.9,
                  adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0, atss_topk=None,
                  layerwise_trust=False, trust_coeff=None):
@@ -59,13 +60,16 @@ class Trainer:
         # match_iou_threshold: threshold matching behind the bipartite match (MultiboxLoss; None = the reference's match alone)
         # focal_gamma / focal_alpha: focal loss on the confidence term (MultiboxLoss; None = the reference's loss)
         # loc_loss / loc_beta: the location term of a positive (MultiboxLoss; None = the reference's L2)
+        # quality_target / quality_gamma / quality_neg_weight: the IoU as the positives' confidence target, by the quality focal
+        # or the varifocal loss (MultiboxLoss; None = off)
         # atss_topk: ATSS matching behind the bipartite match (MultiboxLoss; None = off).  Its pyramid levels are the
         # network's heads: op.head = (cells, k, off), the offsets mbx_head_gather_all uses, in prediction order
         prior_levels = None if atss_topk is None else [op.head[2] for op in net.heads] + [net.P]
         self.loss = MultiboxLoss(bbox_priors, net.B, max_num_bboxes, location_loss_alpha, device=net.dev,
                                  neg_per_pos=neg_per_pos, min_neg=min_neg, match_iou_threshold=match_iou_threshold,
                                  focal_gamma=focal_gamma, focal_alpha=focal_alpha, loc_loss=loc_loss, loc_beta=loc_beta,
-                                 atss_topk=atss_topk, prior_levels=prior_levels)
+                                 atss_topk=atss_topk, prior_levels=prior_levels, quality_target=quality_target,
+                                 quality_gamma=quality_gamma, quality_neg_weight=quality_neg_weight)
         assert self.loss.P == net.P, "priors (%d) do not match the network's predictions (%d)" % (self.loss.P, net.P)
         self.loss.d_locs, self.loss.d_logits = net.d_locs, net.d_logits
         self.lr0, self.dsteps, self.lr_factor, self.staircase = initial_learning_rate, decay_steps_, learning_rate_decay_factor, staircase
@@ -776,3 +780,12 @@ class Trainer:
         """Mean over the batch of the priors ATSS matching added to the last step's bipartite match, or None without it --
         host sync; call it at logging intervals."""
         return None if self.loss.n_atss is None else float(self.loss.n_atss.float().mean())
+
+    def mean_positive_iou(self):
+        """The mean IoU of the last step's positives with their boxes over the batch (the targets of quality_target: the sum
+        of q over the sum of the counts of MultiboxLoss.q_stats), 0.0 when there was no positive, or None without the
+        switch -- host sync; call it at logging intervals."""
+        if self.loss.q_stats is None:
+            return None
+        total, count = self.loss.q_stats.sum(0).tolist()
+        return total / count if count else 0.0

@@ -161,6 +161,47 @@ int mbx_match_atss(const float* priors /*[P,4] x1,y1,x2,y2*/, const int32_t* lev
                    int32_t* match /*[B,P] IN/OUT: mbx_match's output*/, int32_t* n_extra /*[B] or NULL*/,
                    double* thr /*[B,G] or NULL*/, mbx_stream_t stream);
 
+/* IGNORE BAND behind the matching (RetinaNet, Lin et al. 2017: positive at or over 0.5, negative under 0.4, neither in
+ * between; Faster R-CNN's RPN and SSD derivatives likewise, YOLOv3 by the prediction's overlap; optional, not in the
+ * reference, off unless the caller asks).  A prior that sits on an object but is not the one the matcher picked is not
+ * background: it gets a third state, MBX_MATCH_IGNORED, and mbx_loss_fwd_bwd_ignore leaves it out of the confidence loss.
+ * Runs behind mbx_match, and behind mbx_match_extend or mbx_match_atss when one of them runs; `match` is their output and is
+ * updated in place.  `boxes` are what the overlap is judged by, as corners (x1, y1, x2, y2):
+ *   per_image == 0: [P,4], the PRIORS themselves, shared by all images;
+ *   per_image != 0: [B,P,4], image b reads its own row -- a caller passes the decoded predictions here (YOLOv3's rule).  The
+ *   formula is applied to the corners as they are, nothing is put in order first: a degenerate or non-finite prediction is
+ *   whatever the formula and the comparisons below make of it.
+ * Per image b, with n = n_gt[b]:
+ *   status[b] != 0, n <= 0 or n > G: the image is SKIPPED, its row of `match` stays byte for byte as it was and
+ *   n_ignored[b] = 0 (mbx_match_extend's skip rule).
+ *   Otherwise, for every prior p with match[b,p] == MBX_MATCH_FREE (-1) exactly, e its box, and the boxes j in [0, n): the IoU
+ *   in float64 on the float32 inputs widened to double, mbx_match_extend's formula term by term, e first:
+ *     iw = min(e.x2, j.x2) - max(e.x1, j.x1), ih likewise;  inter = iw > 0 && ih > 0 ? iw * ih : 0
+ *     area = (x2 - x1) * (y2 - y1);  uni = area_e + area_j - inter;  iou = uni > 0 ? inter / uni : 0
+ *   If iou >= (double)iou_threshold -- NOT strict -- for any j, match[b,p] = MBX_MATCH_IGNORED (-2).  Only whether some box
+ *   reaches the threshold matters, so the walk over j stops at the first that does.  A NaN IoU passes nothing.
+ *   The quotient is the float64 inter / uni that mbx_match_extend compares: with the priors as `boxes`, `> hi` there and
+ *   `>= lo` here (lo <= hi) split the free priors without a gap or an overlap -- every prior that mbx_match_extend left
+ *   free and whose largest IoU lies in [lo, hi] is ignored, and none that it took.
+ *   A prior with match >= 0 keeps its box and one with match <= -2 its value: a second call changes nothing.  Rows j >= n of
+ *   `gt` are padding and are never read: a NaN there changes nothing.
+ *   n_ignored[b] = the number of priors newly ignored in image b.  Every n_ignored[b] is written on every call (no memset by
+ *   the caller); n_ignored may be NULL.
+ * An image's row depends on its own inputs only -- not on B or its place in the launch -- and the same input gives the same
+ * bytes on every call (no floating-point atomics, the count is a wave and LDS reduction).
+ * NULL boxes / gt / n_gt / status / match, B < 0, P <= 0, G <= 0 or an iou_threshold not in (0, 1] (NaN included):
+ * MBX_ERR_INVALID_ARG; G > 1536 (the staged boxes, 40 bytes each, would not fit the LDS of a plain launch):
+ * MBX_ERR_UNSUPPORTED; nothing is launched or written either way.  B == 0: MBX_OK.  One launch on `stream`, one workgroup
+ * per image, no workspace, graph-capturable.
+ * The five loss entries from before the band read a negative `match` as a negative, -2 included: a caller that runs this
+ * uses mbx_loss_fwd_bwd_ignore.
+ * What the band does to AP on real data is NOT measured here: no trained model or dataset is at hand.                     */
+enum { MBX_MATCH_FREE = -1, MBX_MATCH_IGNORED = -2 };
+int mbx_match_ignore(const float* boxes /*[P,4], or [B,P,4] when per_image*/, int per_image,
+                     const float* gt /*[B,G,4]*/, const int32_t* n_gt /*[B]*/,
+                     const int32_t* status /*[B], as mbx_match left it*/, float iou_threshold, int B, int P, int G,
+                     int32_t* match /*[B,P] IN/OUT*/, int32_t* n_ignored /*[B] or NULL*/, mbx_stream_t stream);
+
 /* ---------------------------------------------------------------- loss fwd+bwd (A7)
  * loss.py:88-101 given the matching: loc_loss = alpha * 1/2 sum (decoded-gt)^2 over
  * matched rows; conf_loss = -sum log(c_matched) - sum log(1 - c_unmatched + 1e-10),
@@ -344,6 +385,40 @@ int mbx_loss_fwd_bwd_quality(const float* decoded /*[B,P,4]*/, const float* conf
                              int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
                              double* q_stats /*[B,2] or NULL*/,
                              void* workspace, size_t workspace_bytes, mbx_stream_t stream);
+
+/* mbx_loss_fwd_bwd_quality with the IGNORE BAND of mbx_match_ignore (optional, not in the reference, off unless the caller
+ * asks): the one entry for every combination of location term, mining, confidence term and band.  Every argument is
+ * mbx_loss_fwd_bwd_quality's, same order and meaning -- MBX_QUALITY_NONE with gamma == 0 and weights (1, 1) is the plain
+ * confidence term, q_stats must be NULL with MBX_QUALITY_NONE -- and `match` has three states:
+ *   match[b,p] >= 0: a positive of that box;
+ *   match[b,p] == MBX_MATCH_IGNORED (-2): neither.  The prior adds nothing to loss2[0] or loss2[1]; its d_raw_locs are
+ *     (0,0,0,0) and its d_logits is +0.0f whatever the sign of grad_scale; it is no candidate of the mining's select and no
+ *     positive; it does not enter q_stats;
+ *   any other negative value (-1, -3, -77, ...): a negative, as in the other entries.
+ * With ign = the number of ignored priors of image b and n_pos its positives:  N_neg = P - n_pos - ign, and
+ *   neg_per_pos == 0: every negative counts, n_neg[b] = N_neg;
+ *   neg_per_pos >= 1: K = min(N_neg, max(min_neg, neg_per_pos * n_pos)), the first K of the negatives in
+ *     mbx_loss_fwd_bwd_mined's order (the same key on conf_in, the index as the tie-break) are selected, n_neg[b] = K.
+ * The outputs are those of mbx_loss_fwd_bwd_quality on the image with its ignored priors REMOVED (taking priors out keeps the
+ * others' relative index order, so the selection is the same set): d_raw_locs and d_logits of every kept prior, n_neg and the
+ * count in q_stats are byte-identical to that call; loss2 and the sum in q_stats are the same terms summed in another lane
+ * order.  With no -2 in `match`, every output is byte-identical to mbx_loss_fwd_bwd_quality on the same arguments.
+ * An image's outputs depend on its own row only, and the same input gives the same bytes on every call.  Any P.
+ * Anything mbx_loss_fwd_bwd_quality rejects: MBX_ERR_INVALID_ARG; workspace_bytes < mbx_loss_ignore_workspace_bytes(B, P):
+ * MBX_ERR_WORKSPACE (a bad argument is reported first); nothing is launched or written either way.  Two launches on
+ * `stream`, one workgroup per image, graph-capturable.
+ * What the band does to AP on real data is NOT measured here: no trained model or dataset is at hand.                  */
+size_t mbx_loss_ignore_workspace_bytes(int B, int P);
+int mbx_loss_fwd_bwd_ignore(const float* decoded /*[B,P,4]*/, const float* conf_in /*[B,P]*/,
+                            int conf_is_logit, const float* gt /*[B,G,4]*/,
+                            const int32_t* match /*[B,P]: >= 0, MBX_MATCH_IGNORED or another negative*/, float alpha,
+                            float grad_scale, int B, int P, int G, float* loss2 /*[2]*/,
+                            float* d_raw_locs /*[B,P,4] or NULL*/, float* d_logits /*[B,P] or NULL*/,
+                            int loc_type /*MBX_LOC_*/, float loc_beta /*MBX_LOC_SMOOTH_L1 only*/,
+                            int quality /*MBX_QUALITY_*/, float gamma, float w_pos, float w_neg,
+                            int neg_per_pos /*0 = every negative counts*/, int min_neg, int32_t* n_neg /*[B] or NULL*/,
+                            double* q_stats /*[B,2] or NULL*/,
+                            void* workspace, size_t workspace_bytes, mbx_stream_t stream);
 
 /* ------------------------------------------------- detect post-processing (A9-A12)
  * Replaces the per-patch numpy loop detect.py:408-436: decode + clip [0,1]

@@ -48,6 +48,9 @@ _SIGS = {
     "mbx_loss_fwd_bwd_loc": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, I, F, F, F, F, I, I, P, P, SZ, P]),
     "mbx_loss_quality_workspace_bytes": (SZ, [I, I]),
     "mbx_loss_fwd_bwd_quality": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, I, F, I, F, F, F, I, I, P, P, P, SZ, P]),
+    "mbx_match_ignore": (I, [P, I, P, P, P, F, I, I, I, P, P, P]),
+    "mbx_loss_ignore_workspace_bytes": (SZ, [I, I]),
+    "mbx_loss_fwd_bwd_ignore": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, I, F, I, F, F, F, I, I, P, P, P, SZ, P]),
     "mbx_decode_filter_topk": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "mbx_nms": (I, [P, P, P, P, I, I, C.c_double, P]),
     "mbx_merge_detections": (I, [P, P, P, P, I, I, I, C.c_double, P, P, P, P, P, P]),

@@ -192,6 +192,40 @@ def quality_loss(cfg):
     return {"quality_target": target, "quality_gamma": float(gamma), "quality_neg_weight": float(w_neg)}
 
 
+IGNORE_SOURCES = ("prior", "prediction")
+
+
+def ignore_band(cfg):
+    """An ignore band for near-object priors in the confidence loss (mbx_match_ignore / mbx_loss_fwd_bwd_ignore; not in the
+    reference, so off when absent): None, or a dict of Trainer keyword arguments.
+      LOSS_IGNORE_IOU_THRESHOLD  a number in (0, 1]; absent or null = off.  A prior the matching left free that overlaps some
+        box of its image by at least the key adds nothing to the confidence loss, gets no gradient and is neither a
+        candidate nor a positive for mining (RetinaNet's band: positive at or over 0.5, negative under 0.4, neither between).
+      LOSS_IGNORE_SOURCE         prior (default): the overlap is the prior's own; prediction: the decoded prediction's
+        (YOLOv3's rule).  Only with the threshold.
+    Together with LOSS_MATCH_IOU_THRESHOLD and source prior, a threshold above the matching threshold raises ValueError
+    naming both keys: every free prior is at or under the matching threshold, so the band would be empty.  A bool, a
+    string, a list, a NaN or a value outside (0, 1] for the threshold, a source that is no such string, or the source
+    without the threshold raises ValueError naming the key.  Composes with LOSS_MATCH_ATSS_TOPK, LOSS_NEG_PER_POS, the focal,
+    location and quality keys.  Host code only."""
+    v, source = cfg.get("LOSS_IGNORE_IOU_THRESHOLD"), cfg.get("LOSS_IGNORE_SOURCE")
+    if v is None:
+        if source is not None:
+            raise ValueError("LOSS_IGNORE_SOURCE is given without LOSS_IGNORE_IOU_THRESHOLD")
+        return None
+    if not (isinstance(v, (int, float)) and not isinstance(v, bool) and 0 < v <= 1):
+        raise ValueError("LOSS_IGNORE_IOU_THRESHOLD must be a number in (0, 1], got %r" % (v,))
+    if source is None:
+        source = "prior"
+    elif not (isinstance(source, str) and source in IGNORE_SOURCES):
+        raise ValueError("LOSS_IGNORE_SOURCE must be one of %s, got %r" % (", ".join(IGNORE_SOURCES), source))
+    hi = match_iou_threshold(cfg)
+    if hi is not None and source == "prior" and v > hi:
+        raise ValueError("LOSS_IGNORE_IOU_THRESHOLD %r is above LOSS_MATCH_IOU_THRESHOLD %r: no free prior overlaps a box by "
+                         "that much, the band would be empty" % (v, hi))
+    return {"ignore_iou_threshold": float(v), "ignore_source": source}
+
+
 def grad_clip(cfg):
     """Global-norm gradient clipping and the non-finite-step guard (mbx_grad_sqnorm / mbx_clip_finalize /
     mbx_rmsprop_ema_step_clipped; not in the reference, so off when absent): None, or CLIP_GRADIENT_NORM as a float > 0

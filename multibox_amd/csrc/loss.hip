@@ -263,6 +263,70 @@ match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict_
   }
 }
 
+// -------------------------------------------------------------------- ignore band
+// The third state of a prior, behind match_kernel and behind match_extend_kernel / match_atss_kernel when one of them runs
+// (mbx_match_ignore, mbx.h has the rule): a prior that is still free (match == MBX_MATCH_FREE exactly) and overlaps some box
+// of its image by at least `thr` becomes MBX_MATCH_IGNORED, which the loss of mbx_loss_fwd_bwd_ignore leaves out.  The frame
+// is match_extend_kernel's: one workgroup per image, blockDim.x a multiple of 64, the image's n boxes and their areas
+// widened to float64 into LDS once (StagedBox, 40 B a box), a thread keeps its box and area in registers and walks the staged
+// boxes (a broadcast read).  The IoU is match_extend_kernel's, line by line -- the same float64 inter / uni, so that `>= thr`
+// here and `> thr` there split the free priors without a gap or an overlap -- but there is no argmax: the walk stops at the
+// first box that reaches the threshold.  A pair that does not overlap has IoU 0, never at a threshold > 0; a NaN fails
+// every comparison on the way and passes nothing.  `image_stride` is 0 (the priors, shared by all images) or P (a row of
+// boxes per image: the decoded predictions, taken as they are).
+__global__ void __launch_bounds__(1024)
+match_ignore_kernel(const float4* __restrict__ boxes_in, size_t image_stride, const float4* __restrict__ gt,
+                    const int* __restrict__ n_gt, const int* __restrict__ status, double thr, int P, int G,
+                    int* __restrict__ match, int* __restrict__ n_ignored) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  StagedBox* boxes = reinterpret_cast<StagedBox*>(smem);      // [n]
+  __shared__ int ignored_waves[16];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = (int)blockDim.x;
+  const int n = n_gt[b];
+  if (status[b] != 0 || n <= 0 || n > G) {                    // skipped: the row stays as it is (mbx_match_extend's rule)
+    if (tid == 0 && n_ignored) n_ignored[b] = 0;
+    return;
+  }
+  for (int j = tid; j < n; j += nt) {
+    const float4 q = gt[(size_t)b * G + j];
+    StagedBox s;
+    s.box = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    s.area = box_area(s.box);
+    boxes[j] = s;
+  }
+  __syncthreads();
+  int* mt = match + (size_t)b * P;
+  const float4* own = boxes_in + (size_t)b * image_stride;
+  int ignored = 0;
+  for (int p = tid; p < P; p += nt) {
+    if (mt[p] != MBX_MATCH_FREE) continue;                    // a positive keeps its box, -2 and below stay: a second call is a no-op
+    const float4 q = own[p];
+    const Box e = {(double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    const double area_e = box_area(e);
+    bool hit = false;
+    for (int j = 0; j < n && !hit; ++j) {
+      const Box g = boxes[j].box;
+      const double iw = fmin(e.x2, g.x2) - fmax(e.x1, g.x1), ih = fmin(e.y2, g.y2) - fmax(e.y1, g.y1);
+      if (iw > 0.0 && ih > 0.0) {
+        const double inter = iw * ih;
+        const double uni = area_e + boxes[j].area - inter;
+        const double iou = uni > 0.0 ? inter / uni : 0.0;
+        hit = iou >= thr;
+      }
+    }
+    if (hit) { mt[p] = MBX_MATCH_IGNORED; ++ignored; }
+  }
+  if (!n_ignored) return;
+  ignored = wave_sum(ignored);
+  if ((tid & 63) == 0) ignored_waves[tid >> 6] = ignored;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int w = 0; w < (nt >> 6); ++w) total += ignored_waves[w];
+    n_ignored[b] = total;
+  }
+}
+
 // ------------------------------------------------------------------- ATSS matching
 // Adaptive Training Sample Selection behind match_kernel (mbx_match_atss, mbx.h has the rule): per box the `topk` priors
 // nearest to its centre on every level are its candidates, its threshold is the mean plus the sample standard deviation of
@@ -691,6 +755,9 @@ __device__ __forceinline__ unsigned long long mined_key(float conf_in, int P, in
 // the row (2.6-26 KB: L1 / L2 hits).  The select ends as soon as the bin it lands in is taken whole (its count is what is
 // still needed): with distinct scores that is after 3-4 passes, and at once when K is 0 or every negative is taken.  Index
 // digits above the bits of P-1 are zero for every candidate and are skipped.  K goes to n_neg[b] (n_neg may be null).
+// IGNORE (mbx_loss_fwd_bwd_ignore): a prior with match == MBX_MATCH_IGNORED is no candidate and no positive -- the first
+// pass counts them (a wave sum, then an integer LDS add: any order, one result) and takes them off P before n_pos.
+template <bool IGNORE = false>
 __device__ __forceinline__ unsigned long long mined_select_cut(const int* __restrict__ mt, const float* __restrict__ cf,
                                                                int P, int neg_per_pos, int min_neg, int b,
                                                                int* __restrict__ n_neg) {
@@ -698,7 +765,9 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
   __shared__ unsigned hist[256];
   __shared__ unsigned long long sh_cut;
   __shared__ int sh_need, sh_done;
+  __shared__ int sh_ignored;         // IGNORE only
   const int tid = threadIdx.x;
+  if (IGNORE && tid == 0) sh_ignored = 0;                     // before the first pass's barrier
   unsigned long long cut = 0ull;     // the digits fixed so far, zeros below
   int need = 0;                      // candidates still to take among those that share them
   for (int shift = 56; shift >= 0; shift -= 8) {
@@ -706,10 +775,17 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
     const unsigned long long fixed = shift == 56 ? 0ull : ~0ull << (shift + 8);
     hist[tid] = 0u;
     __syncthreads();
+    int ignored = 0;
     for (int p = tid; p < P; p += kThreads) {
-      if (mt[p] >= 0) continue;
+      const int m = mt[p];
+      if (m >= 0) continue;
+      if (IGNORE && m == MBX_MATCH_IGNORED) { ++ignored; continue; }
       const unsigned long long key = mined_key(cf[p], P, p);
       if (((key ^ cut) & fixed) == 0ull) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+    }
+    if (IGNORE && shift == 56) {
+      ignored = wave_sum(ignored);
+      if ((tid & 63) == 0 && ignored) atomicAdd(&sh_ignored, ignored);
     }
     __syncthreads();
     if (tid < 64) {                  // lane l owns bins 4l .. 4l+3; `incl` = candidates in its bins and all higher ones
@@ -723,7 +799,7 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
       }
       bool whole = false;            // the answer is known without looking at a bin: nothing, or every negative
       if (shift == 56) {             // first pass: every negative was counted
-        const int n_negatives = (int)__shfl(incl, 0, 64), n_pos = P - n_negatives;
+        const int n_negatives = (int)__shfl(incl, 0, 64), n_pos = P - n_negatives - (IGNORE ? sh_ignored : 0);
         long long K = (long long)neg_per_pos * (long long)n_pos;
         if (K < (long long)min_neg) K = min_neg;
         if (K > (long long)n_negatives) K = n_negatives;
@@ -779,7 +855,12 @@ __device__ __forceinline__ unsigned long long mined_select_cut(const int* __rest
 //     loc_type.  The negatives run the float32 lines below unchanged: their d_logits are loss_loc_kernel's bytes.  q is
 //     taken from loc_axis here, not handed over by loc_term: the location lines stay what they are.  Without QUALITY
 //     `quality` and q_stats are not read and nothing of this is compiled in.
-template <bool MINED, bool FOCAL, bool LOC_ANY, bool QUALITY>
+//   IGNORE (with FOCAL and LOC_ANY; mbx_loss_fwd_bwd_ignore): a prior with match == MBX_MATCH_IGNORED is neither positive nor
+//     negative -- no term in either sum, d_locs 0 and d_logits +0 whatever the sign of grad_scale, no key in the select
+//     (mined_select_cut<true>), nothing in q_stats; without MINED they are counted and n_neg[b] = P - positives - ignored.
+//     Every other negative value of match is a negative, as without the flag.  One compare per prior and one count; without
+//     IGNORE the compare is a compile-time false and the eight kernels from before the flag keep their code.
+template <bool MINED, bool FOCAL, bool LOC_ANY, bool QUALITY, bool IGNORE = false>
 __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
                                           const float4* __restrict__ gt, const int* __restrict__ match, float alpha,
                                           float grad_scale, int P, int G, int loc_type, float loc_beta, float gamma,
@@ -788,22 +869,27 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
                                           float* __restrict__ d_logits, int* __restrict__ n_neg, int quality,
                                           double* __restrict__ q_stats /*[B,2]*/) {
   static_assert(!QUALITY || FOCAL, "the quality target replaces the focal positive term");
+  static_assert(!IGNORE || (FOCAL && LOC_ANY), "the ignore band has the superset entry only");
   constexpr bool kNegFromPositives = FOCAL && !MINED;        // n_neg[b] = P - positives
+  constexpr bool kCountIgnored = IGNORE && kNegFromPositives;   // ... - ignored
   constexpr bool kCountPositives = kNegFromPositives || QUALITY;
   const int b = blockIdx.x, tid = threadIdx.x;
   unsigned long long cut = 0ull;                             // no key is below 0: every negative counts
-  if (MINED) cut = mined_select_cut(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg, b, n_neg);
+  if (MINED) cut = mined_select_cut<IGNORE>(match + (size_t)b * P, logits + (size_t)b * P, P, neg_per_pos, min_neg, b, n_neg);
   const bool modulated = FOCAL && gamma != 0.0f;
 
   double loc_acc = 0.0, conf_acc = 0.0, q_acc = 0.0;
-  int n_pos = 0;
+  int n_pos = 0, n_ign = 0;
   for (int p = tid; p < P; p += kThreads) {
     const size_t i = (size_t)b * P + p;
     const int m = match[i];
     const float z = logits[i];
     float4 dl = make_float4(0.f, 0.f, 0.f, 0.f);
     float g;
-    if (MINED && m < 0 && mined_key(z, P, p) < cut) {
+    if (IGNORE && m == MBX_MATCH_IGNORED) {
+      g = 0.f;                                              // neither positive nor negative: no loss, +0 whatever grad_scale is
+      if (kCountIgnored) ++n_ign;
+    } else if (MINED && m < 0 && mined_key(z, P, p) < cut) {
       g = 0.f;                                              // an unselected negative: no loss, +0 whatever grad_scale is
     } else {
       const float s = is_logit ? 1.0f / (1.0f + expf(-z)) : z;
@@ -854,11 +940,14 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
   if (QUALITY) q_acc = wave_sum(q_acc);
   __shared__ double red[kWaves][QUALITY ? 3 : 2];
   __shared__ int pos_waves[kWaves];
+  __shared__ int ign_waves[kWaves];                          // kCountIgnored only
   if (kCountPositives) n_pos = wave_sum(n_pos);
+  if (kCountIgnored) n_ign = wave_sum(n_ign);
   if ((tid & 63) == 0) {
     red[tid >> 6][0] = loc_acc; red[tid >> 6][1] = conf_acc;
     if (QUALITY) red[tid >> 6][QUALITY ? 2 : 0] = q_acc;
     if (kCountPositives) pos_waves[tid >> 6] = n_pos;
+    if (kCountIgnored) ign_waves[tid >> 6] = n_ign;
   }
   __syncthreads();
   if (tid == 0) {
@@ -869,7 +958,10 @@ __device__ __forceinline__ void loss_body(const float4* __restrict__ decoded, co
     int total = 0;
     if (kCountPositives)
       for (int w = 0; w < kWaves; ++w) total += pos_waves[w];
-    if (kNegFromPositives && n_neg) n_neg[b] = P - total;    // every negative counts
+    int ignored = 0;
+    if (kCountIgnored)
+      for (int w = 0; w < kWaves; ++w) ignored += ign_waves[w];
+    if (kNegFromPositives && n_neg) n_neg[b] = P - total - ignored;    // every negative counts
     if (QUALITY && q_stats) {                                // the wavefronts' sums in their fixed order: the same bytes every call
       double qs = 0.0;
       for (int w = 0; w < kWaves; ++w) qs += red[w][QUALITY ? 2 : 0];
@@ -930,6 +1022,19 @@ loss_quality_kernel(const float4* __restrict__ decoded, const float* __restrict_
                     float* __restrict__ d_logits, int* __restrict__ n_neg, double* __restrict__ q_stats /*[B,2]*/) {
   loss_body<MINED, true, true, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta, gamma,
                                      w_pos, w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg, quality, q_stats);
+}
+
+// mbx_loss_fwd_bwd_ignore: loss_loc_kernel<MINED> (QUALITY = false) or loss_quality_kernel<MINED> with the ignore band.
+template <bool MINED, bool QUALITY>
+__global__ void __launch_bounds__(kThreads)
+loss_ignore_kernel(const float4* __restrict__ decoded, const float* __restrict__ logits, int is_logit,
+                   const float4* __restrict__ gt, const int* __restrict__ match, float alpha, float grad_scale,
+                   int P, int G, int loc_type, float loc_beta, int quality, float gamma, float w_pos, float w_neg,
+                   int neg_per_pos, int min_neg, double* __restrict__ partial /*[B,2]*/, float4* __restrict__ d_locs,
+                   float* __restrict__ d_logits, int* __restrict__ n_neg, double* __restrict__ q_stats /*[B,2]*/) {
+  loss_body<MINED, true, true, QUALITY, true>(decoded, logits, is_logit, gt, match, alpha, grad_scale, P, G, loc_type, loc_beta,
+                                              gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, d_locs, d_logits, n_neg,
+                                              quality, q_stats);
 }
 
 }  // namespace
@@ -1018,6 +1123,23 @@ static int atss_plan(int P, int G, int n_levels, const int32_t* level_start, int
   return MBX_ERR_UNSUPPORTED;
 }
 
+extern "C" int mbx_match_ignore(const float* boxes, int per_image, const float* gt, const int32_t* n_gt,
+                                const int32_t* status, float iou_threshold, int B, int P, int G, int32_t* match,
+                                int32_t* n_ignored, mbx_stream_t stream) {
+  if (!boxes || !gt || !n_gt || !status || !match || B < 0 || P <= 0 || G <= 0) return MBX_ERR_INVALID_ARG;
+  if (!(iou_threshold > 0.0f && iou_threshold <= 1.0f)) return MBX_ERR_INVALID_ARG;      // a NaN fails both
+  const size_t lds = (size_t)G * sizeof(StagedBox);
+  if (lds > 60 * 1024) return MBX_ERR_UNSUPPORTED;           // G > 1536, as mbx_match_extend
+  if (B == 0) return MBX_OK;
+  const int nthreads = P >= 1024 ? 1024 : (P + 63) / 64 * 64;
+  MBX_ENTER();
+  hipLaunchKernelGGL(match_ignore_kernel, dim3(B), dim3(nthreads), lds, mbx_s(stream),
+                     reinterpret_cast<const float4*>(boxes), per_image ? (size_t)P : (size_t)0,
+                     reinterpret_cast<const float4*>(gt), n_gt, status, (double)iou_threshold, P, G, match, n_ignored);
+  MBX_LAUNCH_CHECK();
+  return MBX_OK;
+}
+
 extern "C" int mbx_match_atss_supported(int P, int G, int n_levels, const int32_t* level_start, int topk) {
   return atss_plan(P, G, n_levels, level_start, topk, nullptr, nullptr, nullptr);
 }
@@ -1046,12 +1168,14 @@ extern "C" size_t mbx_loss_mined_workspace_bytes(int B, int) { return mbx_loss_w
 extern "C" size_t mbx_loss_focal_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 extern "C" size_t mbx_loss_loc_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 extern "C" size_t mbx_loss_quality_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
+extern "C" size_t mbx_loss_ignore_workspace_bytes(int B, int) { return mbx_loss_workspace_bytes(B); }
 
-// What the five loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
+// What the six loss entries share: the argument and workspace checks (every entry needs mbx_loss_workspace_bytes(B)),
 // the kernel of `kind`, then loss_final_kernel.  An entry checks its own arguments first; those and the ones here all
 // answer MBX_ERR_INVALID_ARG, so a bad argument still goes before a bad workspace.  Focal, loc and quality mine iff
-// neg_per_pos != 0; loc_type is MBX_LOC_L2 for every kind but kLoc and kQuality; quality and q_stats are kQuality's.
-enum class LossKind { kPlain, kMined, kFocal, kLoc, kQuality };
+// neg_per_pos != 0; loc_type is MBX_LOC_L2 for every kind but kLoc, kQuality and kIgnore; quality and q_stats are kQuality's
+// and kIgnore's (kIgnore with MBX_QUALITY_NONE is the loc kernel's body with the ignore band).
+enum class LossKind { kPlain, kMined, kFocal, kLoc, kQuality, kIgnore };
 
 static int launch_loss(LossKind kind, const float* decoded, const float* logits, int conf_is_logit, const float* gt,
                        const int32_t* match, float alpha, float grad_scale, int B, int P, int G, float* loss2,
@@ -1089,6 +1213,14 @@ static int launch_loss(LossKind kind, const float* decoded, const float* logits,
                          mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha, grad_scale, P, G, loc_type, loc_beta,
                          quality, gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, dl4, d_logits, n_neg, q_stats);
       break;
+    case LossKind::kIgnore: {
+      auto kernel = quality != MBX_QUALITY_NONE ? (neg_per_pos ? loss_ignore_kernel<true, true> : loss_ignore_kernel<false, true>)
+                                                : (neg_per_pos ? loss_ignore_kernel<true, false> : loss_ignore_kernel<false, false>);
+      hipLaunchKernelGGL(kernel, dim3(B), dim3(kThreads), 0, mbx_s(stream), dec4, logits, conf_is_logit, gt4, match, alpha,
+                         grad_scale, P, G, loc_type, loc_beta, quality, gamma, w_pos, w_neg, neg_per_pos, min_neg, partial, dl4,
+                         d_logits, n_neg, q_stats);
+      break;
+    }
   }
   MBX_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, mbx_s(stream), partial, B, alpha,
@@ -1163,6 +1295,23 @@ extern "C" int mbx_loss_fwd_bwd_quality(const float* decoded, const float* logit
   if (loc_type == MBX_LOC_SMOOTH_L1 && !(loc_beta > 0.0f && !isinf(loc_beta))) return MBX_ERR_INVALID_ARG;   // a NaN fails
   if (!focal_arguments_ok(gamma, w_pos, w_neg, neg_per_pos, min_neg)) return MBX_ERR_INVALID_ARG;
   return launch_loss(LossKind::kQuality, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
+                     d_raw_locs, d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
+                     workspace_bytes, stream, quality, q_stats);
+}
+
+extern "C" int mbx_loss_fwd_bwd_ignore(const float* decoded, const float* logits, int conf_is_logit, const float* gt,
+                                       const int32_t* match, float alpha, float grad_scale, int B, int P, int G,
+                                       float* loss2, float* d_raw_locs, float* d_logits, int loc_type, float loc_beta,
+                                       int quality, float gamma, float w_pos, float w_neg, int neg_per_pos, int min_neg,
+                                       int32_t* n_neg, double* q_stats, void* workspace, size_t workspace_bytes,
+                                       mbx_stream_t stream) {
+  if (quality < MBX_QUALITY_NONE || quality > MBX_QUALITY_VFL) return MBX_ERR_INVALID_ARG;
+  if (quality == MBX_QUALITY_NONE && q_stats) return MBX_ERR_INVALID_ARG;
+  if (quality == MBX_QUALITY_QFL && gamma > 0.0f && gamma < 1.0f) return MBX_ERR_INVALID_ARG;   // as mbx_loss_fwd_bwd_quality
+  if (loc_type < MBX_LOC_L2 || loc_type > MBX_LOC_CIOU) return MBX_ERR_INVALID_ARG;
+  if (loc_type == MBX_LOC_SMOOTH_L1 && !(loc_beta > 0.0f && !isinf(loc_beta))) return MBX_ERR_INVALID_ARG;   // a NaN fails
+  if (!focal_arguments_ok(gamma, w_pos, w_neg, neg_per_pos, min_neg)) return MBX_ERR_INVALID_ARG;
+  return launch_loss(LossKind::kIgnore, decoded, logits, conf_is_logit, gt, match, alpha, grad_scale, B, P, G, loss2,
                      d_raw_locs, d_logits, loc_type, loc_beta, gamma, w_pos, w_neg, neg_per_pos, min_neg, n_neg, workspace,
                      workspace_bytes, stream, quality, q_stats);
 }

@@ -61,6 +61,23 @@ def extend_matches(priors, gt_bboxes, num_gt_bboxes, status, match, iou_threshol
     return match, n_extra
 
 
+def ignore_matches(boxes, gt_bboxes, num_gt_bboxes, status, match, iou_threshold, n_ignored=None):
+    """mbx_match_ignore (the ignore band behind the matching): boxes [P,4] corners -- the priors, shared by all images -- or
+    [B,P,4], a row per image (the decoded predictions), gt [B,G,4], n [B], status [B] as mbx_match left it, match int32
+    [B,P] updated IN PLACE -- every prior still free (-1) that overlaps some box of its image by at least iou_threshold, in
+    (0, 1], becomes -2 (MBX_MATCH_IGNORED), which mbx_loss_fwd_bwd_ignore leaves out of the confidence loss.  n_ignored
+    int32 [B] (optional) receives the number ignored per image.  Returns (match, n_ignored)."""
+    B, P = match.shape
+    G = gt_bboxes.shape[1]
+    assert boxes.shape in ((P, 4), (B, P, 4)) and gt_bboxes.shape == (B, G, 4)
+    _lib.check(_lib.lib().mbx_match_ignore(_f32(boxes).data_ptr(), int(boxes.dim() == 3), _f32(gt_bboxes).data_ptr(),
+                                           _i32(num_gt_bboxes).data_ptr(), _i32(status).data_ptr(), float(iou_threshold),
+                                           B, P, G, _i32(match).data_ptr(),
+                                           None if n_ignored is None else _i32(n_ignored).data_ptr(), _stream()),
+               "mbx_match_ignore")
+    return match, n_ignored
+
+
 def _level_table(level_start):
     """level_start as the int32 HOST array mbx_match_atss takes, and its number of levels."""
     levels = [int(v) for v in level_start]
@@ -170,6 +187,24 @@ def _quality_arguments(quality_target, quality_gamma, quality_neg_weight):
     return QUALITY_TARGETS.index(quality_target) + 1, float(gamma), 1.0, float(w_neg)
 
 
+IGNORE_SOURCES = ("prior", "prediction")
+
+
+def _ignore_arguments(ignore_iou_threshold, ignore_source):
+    """None (off), or (threshold, per_image) as mbx_match_ignore takes them.  Raises ValueError on a bad value."""
+    if not (isinstance(ignore_source, str) and ignore_source in IGNORE_SOURCES):
+        raise ValueError("ignore_source must be one of %s, got %r" % (", ".join(IGNORE_SOURCES), ignore_source))
+    if ignore_iou_threshold is None:
+        if ignore_source != "prior":
+            raise ValueError("ignore_source is given without ignore_iou_threshold")
+        return None
+    v = ignore_iou_threshold
+    # the entry takes a float32: the value has to be in (0, 1] as one
+    if not (isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 < ctypes.c_float(v).value <= 1.0):
+        raise ValueError("ignore_iou_threshold must be a number in (0, 1] (as a float32), got %r" % (v,))
+    return float(v), int(ignore_source == "prediction")
+
+
 class MultiboxLoss:
     """Fused decode + match + loss (+ gradients) with preallocated buffers (no allocation per step).
 
@@ -211,14 +246,29 @@ class MultiboxLoss:
     (finite and > 0; default 1 under "qfl", 0.75 under "varifocal") weighs the negatives; both only with the target.  Not
     together with focal_gamma / focal_alpha: each decides the confidence term.  The sum of the positives' IoUs and their
     number per image are left in ``q_stats`` ([B, 2] float64).  Scores trained this way estimate localisation quality as
-    well as objectness.  What that does to AP on real data is not measured here either."""
+    well as objectness.  What that does to AP on real data is not measured here either.
+
+    ignore_iou_threshold (a float in (0, 1]; None = off): the ignore band -- behind the matching above every prior still
+    free that overlaps some box of its image by at least the threshold is neither positive nor negative: no confidence
+    loss, no gradient, no candidate and no positive for mining (mbx_match_ignore writes -2 into ``match``,
+    mbx_loss_fwd_bwd_ignore, the one entry for every combination with the switches above, leaves those out; include/mbx.h);
+    their number per image is left in ``n_ignored``.  ignore_source ("prior", the default, or "prediction"; only with the
+    threshold) says whose overlap counts: the prior's own, or the decoded prediction's (YOLOv3's rule).  With
+    match_iou_threshold and source "prior" the threshold must not be above it: no free prior overlaps a box by more.  What
+    that does to AP on real data is not measured here either."""
 
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
                  min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
-                 atss_topk=None, prior_levels=None, quality_target=None, quality_gamma=None, quality_neg_weight=None):
+                 atss_topk=None, prior_levels=None, quality_target=None, quality_gamma=None, quality_neg_weight=None,
+                 ignore_iou_threshold=None, ignore_source="prior"):
         self.focal = _focal_arguments(focal_gamma, focal_alpha)
         self.loc = _loc_arguments(loc_loss, loc_beta)
         self.quality = _quality_arguments(quality_target, quality_gamma, quality_neg_weight)
+        self.ignore = _ignore_arguments(ignore_iou_threshold, ignore_source)
+        if self.ignore is not None and match_iou_threshold is not None and not self.ignore[1] \
+                and isinstance(match_iou_threshold, (int, float)) and self.ignore[0] > match_iou_threshold:
+            raise ValueError("ignore_iou_threshold %r is above match_iou_threshold %r: no free prior overlaps a box by that "
+                             "much, the band would be empty" % (ignore_iou_threshold, match_iou_threshold))
         if self.quality is not None and self.focal is not None:
             raise ValueError("quality_target and focal_gamma / focal_alpha are both given: each decides the confidence term")
         self.priors = torch.as_tensor(bbox_priors, dtype=torch.float32).to(device).contiguous()
@@ -239,8 +289,18 @@ class MultiboxLoss:
             mining = (neg_per_pos, min_neg, self.n_neg.data_ptr())
         # the entry forward_backward calls, the arguments it has between the common ones and the workspace, its workspace
         l = _lib.lib()
-        self.q_stats = None
-        if self.quality is not None:
+        self.q_stats, self.n_ignored = None, None
+        if self.ignore is not None:
+            # the superset entry, whatever else is on: loc, quality and focal defaults filled in as the quality branch does
+            self.n_ignored = torch.zeros((self.B,), dtype=torch.int32, device=device)
+            if self.quality is not None:
+                self.q_stats = torch.zeros((self.B, 2), dtype=torch.float64, device=device)
+            confidence = self.quality or ((0,) + (self.focal or (0.0, 1.0, 1.0)))
+            self.entry = "mbx_loss_fwd_bwd_ignore"
+            self.entry_args = (self.loc or (0, 0.0)) + confidence + mining + \
+                (None if self.q_stats is None else self.q_stats.data_ptr(),)
+            ws_bytes = l.mbx_loss_ignore_workspace_bytes(self.B, self.P)
+        elif self.quality is not None:
             self.q_stats = torch.zeros((self.B, 2), dtype=torch.float64, device=device)
             self.entry = "mbx_loss_fwd_bwd_quality"
             self.entry_args = (self.loc or (0, 0.0)) + self.quality + mining + (self.q_stats.data_ptr(),)
@@ -316,6 +376,11 @@ class MultiboxLoss:
                                         num_gt_bboxes.data_ptr(), self.status.data_ptr(), self.atss_topk, B, P, G,
                                         self.match.data_ptr(), self.n_atss.data_ptr(), self.atss_thr.data_ptr(), s),
                        "mbx_match_atss")
+        if self.ignore is not None:
+            boxes = self.decoded if self.ignore[1] else self.priors
+            _lib.check(l.mbx_match_ignore(boxes.data_ptr(), self.ignore[1], gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),
+                                          self.status.data_ptr(), self.ignore[0], B, P, G, self.match.data_ptr(),
+                                          self.n_ignored.data_ptr(), s), "mbx_match_ignore")
         common = (self.decoded.data_ptr(), _f32(logits).data_ptr(), int(bool(conf_is_logit)), gt_bboxes.data_ptr(),
                   self.match.data_ptr(), self.alpha, float(grad_scale), B, P, G, self.loss2.data_ptr(), self.d_locs.data_ptr(),
                   self.d_logits.data_ptr())

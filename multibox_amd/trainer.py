@@ -50,6 +50,7 @@ class Trainer:
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
                  match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
                  quality_target=None, quality_gamma=None, quality_neg_weight=None,
+                 ignore_iou_threshold=None, ignore_source="prior",
                  clip_gradient_norm=None, optimizer="rmsprop", sgd_momentum=0.9, sgd_nesterov=False, adam_beta1=0.9,
                  adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0, atss_topk=None,
                  layerwise_trust=False, trust_coeff=None):
@@ -62,6 +63,8 @@ class Trainer:
         # loc_loss / loc_beta: the location term of a positive (MultiboxLoss; None = the reference's L2)
         # quality_target / quality_gamma / quality_neg_weight: the IoU as the positives' confidence target, by the quality focal
         # or the varifocal loss (MultiboxLoss; None = off)
+        # ignore_iou_threshold / ignore_source: the ignore band of the confidence loss -- a free prior that overlaps a box by
+        # at least the threshold is neither positive nor negative (MultiboxLoss; None = off)
         # atss_topk: ATSS matching behind the bipartite match (MultiboxLoss; None = off).  Its pyramid levels are the
         # network's heads: op.head = (cells, k, off), the offsets mbx_head_gather_all uses, in prediction order
         prior_levels = None if atss_topk is None else [op.head[2] for op in net.heads] + [net.P]
@@ -69,7 +72,8 @@ class Trainer:
                                  neg_per_pos=neg_per_pos, min_neg=min_neg, match_iou_threshold=match_iou_threshold,
                                  focal_gamma=focal_gamma, focal_alpha=focal_alpha, loc_loss=loc_loss, loc_beta=loc_beta,
                                  atss_topk=atss_topk, prior_levels=prior_levels, quality_target=quality_target,
-                                 quality_gamma=quality_gamma, quality_neg_weight=quality_neg_weight)
+                                 quality_gamma=quality_gamma, quality_neg_weight=quality_neg_weight,
+                                 ignore_iou_threshold=ignore_iou_threshold, ignore_source=ignore_source)
         assert self.loss.P == net.P, "priors (%d) do not match the network's predictions (%d)" % (self.loss.P, net.P)
         self.loss.d_locs, self.loss.d_logits = net.d_locs, net.d_logits
         self.lr0, self.dsteps, self.lr_factor, self.staircase = initial_learning_rate, decay_steps_, learning_rate_decay_factor, staircase
@@ -780,6 +784,11 @@ class Trainer:
         """Mean over the batch of the priors ATSS matching added to the last step's bipartite match, or None without it --
         host sync; call it at logging intervals."""
         return None if self.loss.n_atss is None else float(self.loss.n_atss.float().mean())
+
+    def ignored_per_image(self):
+        """Mean over the batch of the free priors the last step's ignore band took out of the confidence loss, or None
+        without it -- host sync; call it at logging intervals."""
+        return None if self.loss.n_ignored is None else float(self.loss.n_ignored.float().mean())
 
     def mean_positive_iou(self):
         """The mean IoU of the last step's positives with their boxes over the batch (the targets of quality_target: the sum

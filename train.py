@@ -48,7 +48,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, quality_loss, grad_clip, optimizer, atss_matching, layerwise_trust
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, quality_loss, grad_clip, optimizer, atss_matching, layerwise_trust, ignore_band
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -77,6 +77,7 @@ def main():
         focal = focal_loss(cfg)                   # [new] LOSS_FOCAL_GAMMA / LOSS_FOCAL_ALPHA: focal loss, off when absent
         loc_term = loc_loss(cfg)                  # [new] LOSS_LOC_TYPE / LOSS_LOC_BETA: the location term, L2 when absent
         quality = quality_loss(cfg)               # [new] LOSS_QUALITY_TARGET (+ _GAMMA, _NEG_WEIGHT): IoU-aware confidence target, off when absent
+        ignore = ignore_band(cfg)                 # [new] LOSS_IGNORE_IOU_THRESHOLD (+ _SOURCE): ignore band of the confidence loss, off when absent
         clip_norm = grad_clip(cfg)                # [new] CLIP_GRADIENT_NORM: global-norm clipping + non-finite guard, off when absent
         opt = optimizer(cfg)                      # [new] OPTIMIZER (+ its keys) / LEARNING_RATE_WARMUP_STEPS: RMSProp, no warm-up when absent
         trust = layerwise_trust(cfg)              # [new] LAYERWISE_TRUST (+ _COEFF): LARS on sgd, LAMB on adam / adamw, off when absent
@@ -105,7 +106,7 @@ def main():
                  match_iou_threshold=match_iou, focal_gamma=focal[0] if focal else None,
                  focal_alpha=focal[1] if focal else None, loc_loss=loc_term[0] if loc_term else None,
                  loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm, atss_topk=atss_topk, **opt, **(trust or {}),
-                 **(quality or {}))
+                 **(quality or {}), **(ignore or {}))
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -203,6 +204,8 @@ def main():
             rec.update(loc_log_fields(loc_term))
             if quality:
                 rec.update(quality, mean_positive_iou=tr.mean_positive_iou())
+            if ignore:
+                rec.update(ignore, ignored_per_image=tr.ignored_per_image())
             if clip_norm is not None:
                 rec.update(grad_norm=tr.grad_norm(), clip_scale=tr.clip_scale(), clipped_steps=tr.clipped_steps(),
                            nonfinite_steps=tr.nonfinite_steps())

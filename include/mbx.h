@@ -161,6 +161,60 @@ int mbx_match_atss(const float* priors /*[P,4] x1,y1,x2,y2*/, const int32_t* lev
                    int32_t* match /*[B,P] IN/OUT: mbx_match's output*/, int32_t* n_extra /*[B] or NULL*/,
                    double* thr /*[B,G] or NULL*/, mbx_stream_t stream);
 
+/* TASK-ALIGNED MATCHING behind mbx_match (the Task-Aligned Assigner of TOOD, Feng et al., ICCV 2021, also the assigner of
+ * PP-YOLOE, YOLOv6 and YOLOv8; optional, not in the reference, off unless the caller asks; the alternative to
+ * mbx_match_extend and mbx_match_atss -- a caller runs one of the three).  Those two promote a free prior by what the PRIORS
+ * overlap; this one looks at what the network currently PREDICTS: per box it picks the priors whose prediction is already
+ * both confident and well placed, ranked by t = s^alpha * u^beta, s the score and u the IoU of the decoded prediction with
+ * the box.  `priors` are the priors as corners, `decoded` [B,P,4] and `conf` [B,P] are what mbx_match reads (the decoded
+ * predictions as corners, sigmoid + 1e-10), `match` is mbx_match's output and is updated in place.  alpha = alpha_halves / 2
+ * (an integer number of halves in [0, 8], so the power needs products and one square root only), beta an integer in [1, 16];
+ * the paper's setting is topk 13, alpha 1 (alpha_halves 2), beta 6.
+ * All arithmetic is float64 on the float32 inputs widened to double, in exactly this order, no product fused into a sum.
+ * Per image b, with n = n_gt[b]:
+ *   status[b] != 0, n <= 0 or n > G: the image is SKIPPED, its row of `match` stays byte for byte as it was,
+ *   n_extra[b] = 0 and thr[b, :] = 0.0 (mbx_match_extend's skip rule).
+ *   Score of prior p:  s = (double)conf[b,p].
+ *   Overlap of prior p and box j < n:  u = mbx_match_extend's IoU, term by term, with e = decoded[b,p] first and the box second:
+ *     iw = min(e.x2, j.x2) - max(e.x1, j.x1), ih likewise;  inter = iw > 0 && ih > 0 ? iw * ih : 0
+ *     area = (x2 - x1) * (y2 - y1);  uni = area_e + area_j - inter;  u = uni > 0 ? inter / uni : 0
+ *   The corners are used as they are, nothing is put in order first (as mbx_match_ignore with per_image).
+ *   Metric:  r = 1.0; alpha_halves / 2 times: r = r * s;  if alpha_halves is odd: r = r * sqrt(s) (correctly rounded);
+ *            w = 1.0; beta times: w = w * u;   t = r * w.
+ *   CANDIDATES of box j: every prior p whose own centre -- of the PRIOR, cx = (x1 + x2) * 0.5, cy = (y1 + y2) * 0.5 from
+ *   `priors` -- lies strictly inside the box, x1_j < cx && cx < x2_j && y1_j < cy && cy < y2_j (mbx_match_atss's expressions
+ *   and comparisons), and whose t > 0 (a NaN fails).  Priors that mbx_match assigned count as candidates like any other.
+ *   SELECTION: the min(topk, number of candidates) candidates with the largest t; equal t goes to the lowest prior index.
+ *   thr[b,j] = the t of the last one selected, 0.0 where the box has no candidate, and 0.0 for j >= n.
+ *   ASSIGNMENT: every prior with match[b,p] < 0 that at least one box selected gets the box of the largest u, the lowest j
+ *   among equals.  A prior with match[b,p] >= 0 keeps its box.  Rows j >= n of `gt` are never read.
+ *   n_extra[b] = the number of priors newly assigned.  n_extra and thr may each be NULL; every element is written on every
+ *   call (no memset by the caller).
+ * An image's row depends on its own inputs only -- not on B or its place in the launch -- and the same input gives the same
+ * bytes on every call: no floating-point atomics; the claims are resolved as mbx_match_atss resolves them, by an unsigned
+ * 64-bit max on the bit patterns of u in LDS and an unsigned integer min on `match`, neither of which depends on the order of
+ * arrival.
+ * The bipartite match stays in front: every box keeps its one guaranteed prior, and that is what carries training while the
+ * predictions still overlap nothing -- this call then adds nothing.  TOOD's normalised soft target (t scaled per box to the
+ * largest IoU) is NOT part of this entry: mbx_loss_fwd_bwd_quality supplies an IoU target for the confidence.
+ * NULL priors / decoded / conf / gt / n_gt / status / match, B < 0, P <= 0, G <= 0, topk < 1, alpha_halves outside [0, 8] or
+ * beta outside [1, 16]: MBX_ERR_INVALID_ARG.  The launch holds an image in the LDS of a plain launch:
+ *     8 P + 40 G + 64 + 2 G m  <=  65536 bytes,   m = min(topk, P),   and P < 65535
+ * (the claims, the staged boxes, the wavefronts' counts, the selected priors of every box as 2-byte indices); any other
+ * size: MBX_ERR_UNSUPPORTED.  (P = 4221, G = 100, topk = 13 needs 40 KB; P = 646, G = 13 fits at every topk.)  Nothing is
+ * launched or written for either error.  B == 0: MBX_OK.  mbx_match_tal_supported gives the same verdict for a size, on a
+ * host without a GPU too.  No environment variable is read.  One launch on `stream`, one workgroup per image of min(G, 16)
+ * wavefronts, a wavefront per box, no workspace, graph-capturable.  The loss entries read the extended `match` as they read
+ * any other; mining counts its positives from it; mbx_match_ignore may run behind it.
+ * What task-aligned matching does to AP on real data is NOT measured here: no trained model or dataset is at hand.         */
+int mbx_match_tal_supported(int P, int G, int topk);
+int mbx_match_tal(const float* priors /*[P,4] x1,y1,x2,y2*/, const float* decoded /*[B,P,4], as mbx_match reads them*/,
+                  const float* conf /*[B,P] sigmoid + 1e-10, as mbx_match reads it*/, const float* gt /*[B,G,4]*/,
+                  const int32_t* n_gt /*[B]*/, const int32_t* status /*[B], as mbx_match left it*/, int topk,
+                  int alpha_halves /*alpha = alpha_halves / 2, in [0, 8]*/, int beta /*[1, 16]*/, int B, int P, int G,
+                  int32_t* match /*[B,P] IN/OUT: mbx_match's output*/, int32_t* n_extra /*[B] or NULL*/,
+                  double* thr /*[B,G] or NULL*/, mbx_stream_t stream);
+
 /* IGNORE BAND behind the matching (RetinaNet, Lin et al. 2017: positive at or over 0.5, negative under 0.4, neither in
  * between; Faster R-CNN's RPN and SSD derivatives likewise, YOLOv3 by the prediction's overlap; optional, not in the
  * reference, off unless the caller asks).  A prior that sits on an object but is not the one the matcher picked is not

@@ -38,6 +38,8 @@ _SIGS = {
     "mbx_match_extend": (I, [P, P, P, P, F, I, I, I, P, P, P]),
     "mbx_match_atss_supported": (I, [I, I, I, P, I]),
     "mbx_match_atss": (I, [P, P, I, P, P, P, I, I, I, I, P, P, P, P]),
+    "mbx_match_tal_supported": (I, [I, I, I]),
+    "mbx_match_tal": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P]),
     "mbx_loss_workspace_bytes": (SZ, [I]),
     "mbx_loss_fwd_bwd": (I, [P, P, I, P, P, F, F, I, I, I, P, P, P, P, SZ, P]),
     "mbx_loss_mined_workspace_bytes": (SZ, [I, I]),

@@ -20,6 +20,7 @@ ARCH = "gfx950"
 SOURCES = {
     "priors.cpp": ["-ffp-contract=off"],
     "loss.hip": ["-ffp-contract=off"],
+    "match_tal.hip": ["-ffp-contract=off"],
     "postproc.hip": ["-ffp-contract=off"],
     "merge.hip": ["-ffp-contract=off"],
     "cocomatch.hip": ["-ffp-contract=off"],

@@ -102,6 +102,39 @@ def atss_matching(cfg):
     return topk
 
 
+def tal_matching(cfg):
+    """Task-aligned matching behind the bipartite match (mbx_match_tal, TOOD's assigner; not in the reference, so off when
+    absent): None, or the Trainer's keyword arguments {tal_topk, tal_alpha, tal_beta} from
+      LOSS_MATCH_TAL_TOPK   an int >= 1 (13 in the paper); absent or null = off.  Per box the key's number of priors with
+                            their centre inside it whose prediction scores the largest conf^alpha * IoU^beta are selected,
+                            and the free ones become positives of the box their prediction overlaps most.
+      LOSS_MATCH_TAL_ALPHA  a multiple of 0.5 in [0, 4], default 1.0; only with the first.
+      LOSS_MATCH_TAL_BETA   an int in [1, 16], default 6; only with the first.
+    Not together with LOSS_MATCH_IOU_THRESHOLD or LOSS_MATCH_ATSS_TOPK (each decides what a free prior becomes): ValueError
+    naming both keys.  A bool, a string, a list, a NaN or a value out of range raises ValueError naming the key.  Host code
+    only."""
+    if cfg.get("LOSS_MATCH_TAL_TOPK") is None:
+        for key in ("LOSS_MATCH_TAL_ALPHA", "LOSS_MATCH_TAL_BETA"):
+            if cfg.get(key) is not None:
+                raise ValueError("%s is given without LOSS_MATCH_TAL_TOPK" % key)
+        return None
+    topk = _int_key(cfg, "LOSS_MATCH_TAL_TOPK", 1)
+    for key in ("LOSS_MATCH_IOU_THRESHOLD", "LOSS_MATCH_ATSS_TOPK"):
+        if cfg.get(key) is not None:
+            raise ValueError("LOSS_MATCH_TAL_TOPK and %s are both given: choose one matching rule" % key)
+    alpha = cfg.get("LOSS_MATCH_TAL_ALPHA")
+    if alpha is None:
+        alpha = 1.0
+    elif not (isinstance(alpha, (int, float)) and not isinstance(alpha, bool) and 0 <= alpha <= 4 and alpha * 2 == int(alpha * 2)):
+        raise ValueError("LOSS_MATCH_TAL_ALPHA must be a multiple of 0.5 in [0, 4], got %r" % (alpha,))
+    beta = 6
+    if cfg.get("LOSS_MATCH_TAL_BETA") is not None:
+        beta = _int_key(cfg, "LOSS_MATCH_TAL_BETA", 1)
+        if beta > 16:
+            raise ValueError("LOSS_MATCH_TAL_BETA must be an integer in [1, 16], got %r" % (beta,))
+    return {"tal_topk": topk, "tal_alpha": float(alpha), "tal_beta": beta}
+
+
 def focal_loss(cfg):
     """Focal loss on the confidence term (mbx_loss_fwd_bwd_focal; not in the reference, so off when absent): None, or
     (gamma, alpha_or_None) from LOSS_FOCAL_GAMMA (a number in [0, 10]; absent or null = off) and LOSS_FOCAL_ALPHA (a number

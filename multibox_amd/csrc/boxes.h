@@ -13,6 +13,10 @@ struct Box { double x1, y1, x2, y2; };
 
 __device__ __forceinline__ double box_area(const Box& b) { return (b.x2 - b.x1) * (b.y2 - b.y1); }
 
+// A ground-truth box as the matching kernels behind match_kernel stage it in LDS (loss.hip, match_tal.hip): widened to
+// float64 once, with its area (40 B a box).
+struct StagedBox { Box box; double area; };
+
 // IoU of the EARLIER (kept) box e and the later box b, given their areas: term by term
 //   iw = min(e.x2, b.x2) - max(e.x1, b.x1), ih likewise; inter = iw > 0 && ih > 0 ? iw * ih : 0;
 //   uni = area(e) + area(b) - inter (in that order); iou = uni > 0 ? inter / uni : 0

@@ -4,6 +4,7 @@
 // wave64 shuffle reductions.  Built with -ffp-contract=off: the float32 cost arithmetic
 // must keep the reference's rounding sequence (loss.py:21-35).
 #include "boxes.h"
+#include "wave_select.h"
 
 namespace {
 
@@ -208,8 +209,6 @@ match_kernel(const float4* __restrict__ decoded, const float* __restrict__ conf,
 // The IoU is iou_corners' (boxes.h), term by term, with the prior as its first box; a pair that does not overlap has IoU 0,
 // which is never over a threshold > 0, so the float64 division is done for overlapping pairs only.  `best` starts at the
 // threshold and moves on a strictly larger IoU: the lowest j among the largest, and only where that is over the threshold.
-struct StagedBox { Box box; double area; };
-
 __global__ void __launch_bounds__(1024)
 match_extend_kernel(const float4* __restrict__ priors, const float4* __restrict__ gt, const int* __restrict__ n_gt,
                     const int* __restrict__ status, double thr, int P, int G, int* __restrict__ match,
@@ -335,7 +334,7 @@ match_ignore_kernel(const float4* __restrict__ boxes_in, size_t image_stride, co
 //   LDS: claim[P] (8 B: the largest IoU bit pattern a positive box has claimed the prior with) | boxes[G] (StagedBox) |
 //        iou[nw][m] (8 B, a wavefront's scratch) | cand[G][m] (2 B: a box's candidates, then its positives).
 //   Pass 1, a wavefront per box j = wave, wave + nw, ...: per level it finds the cut -- the min(topk, size)-th smallest
-//     (distance key, index) pair.  A strided scan leaves in every lane's registers the kAtssKeep smallest of its own pairs,
+//     (distance key, index) pair (wave_select.h, shared with match_tal.hip).  A strided scan leaves in every lane's registers the kKeepPairs smallest of its own pairs,
 //     in order; each round a 64-lane min over the heads of the lists takes the next pair.  Only when a lane has handed out
 //     its whole list and had more to offer does the wavefront scan again, for the pairs over the last one taken: with topk
 //     9 and the priors of one cell on neighbouring lanes that is one scan a level, not nine (the launch at P = 3199,
@@ -351,15 +350,8 @@ match_ignore_kernel(const float4* __restrict__ boxes_in, size_t image_stride, co
 //     bits) equals claim[p] lowers match[b,p] with an unsigned integer min -- a free entry is negative, as unsigned above
 //     every j -- so the lowest j among the largest IoUs stays; whoever finds the entry still negative counts the prior.
 // Lanes of one wavefront hand LDS values to each other without a workgroup barrier (the wavefronts run different numbers
-// of boxes): wave_lds_sync() keeps the compiler from moving LDS accesses across the hand-off; the hardware runs one
-// wavefront's LDS instructions in order.
+// of boxes): wave_lds_sync() (wave_select.h) stands at each hand-off.
 struct AtssLevels { int start[9]; };                          // level_start by value: at most 8 levels
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Squared centre distance of prior q to (cxj, cyj) as an unsigned key: a non-negative double orders like its bit pattern;
 // a NaN goes behind every number, +inf included.
@@ -370,62 +362,7 @@ __device__ __forceinline__ unsigned long long atss_d2_key(const float4 q, double
   return d2 != d2 ? ~0ull : (d2 == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(d2));
 }
 
-// (key, index) pairs in lexicographic order: equal distances go to the lowest prior index.
-__device__ __forceinline__ bool atss_pair_less(unsigned long long ka, int ia, unsigned long long kb, int ib) {
-  return ka < kb || (ka == kb && ia < ib);
-}
-
-// The smallest (key, index) pair of the wavefront's 64 lanes, in every lane (all 64 active), by data-parallel-primitive
-// moves.  A step: every lane takes the value of the lane the control CTRL names and keeps the smaller; a lane the control
-// gives no source, or whose row ROW_MASK leaves out, sees the identity (all ones).  A shift scan inside each row of 16
-// lanes (row_shr 1, 2, 4, 8), then lane 15 of rows 0 and 2 to rows 1 and 3 (row_bcast15) and lane 31 to rows 2 and 3
-// (row_bcast31) leave the minimum in lane 63, which is read out as a wavefront-uniform value.  The 64-bit keys are reduced
-// first; one lane holds the smallest key unless distances tie, and only then are the tied lanes' indices reduced too.
-// No LDS traffic: the sixteen wavefronts of a workgroup run these rounds at once, and as ds_bpermute shuffles, eighteen a
-// round, they all went through the one LDS of the compute unit (539 -> 490 us at P = 3199, G = 100; LAB_NOTES).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void atss_dpp_min(unsigned long long& k) {
-  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)k, CTRL, ROW_MASK, 0xf, false);
-  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(k >> 32), CTRL, ROW_MASK, 0xf, false);
-  const unsigned long long ok = ((unsigned long long)ohi << 32) | olo;
-  if (ok < k) k = ok;
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void atss_dpp_min(int& i) {
-  const int oi = __builtin_amdgcn_update_dpp(0x7fffffff, i, CTRL, ROW_MASK, 0xf, false);
-  if (oi < i) i = oi;
-}
-template <typename T>
-__device__ __forceinline__ void atss_dpp_min_to_lane63(T& v) {
-  atss_dpp_min<0x111, 0xf>(v);
-  atss_dpp_min<0x112, 0xf>(v);
-  atss_dpp_min<0x114, 0xf>(v);
-  atss_dpp_min<0x118, 0xf>(v);
-  atss_dpp_min<0x142, 0xa>(v);
-  atss_dpp_min<0x143, 0xc>(v);
-}
-
-__device__ __forceinline__ void atss_wave_min(unsigned long long& k, int& i) {
-  unsigned long long mk = k;
-  atss_dpp_min_to_lane63(mk);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mk, 63);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mk >> 32), 63);
-  mk = ((unsigned long long)hi << 32) | lo;
-  const unsigned long long tied = __ballot(k == mk);          // never empty: the lane the minimum came from
-  int mi;
-  if (__popcll(tied) == 1) {
-    mi = __builtin_amdgcn_readlane(i, __ffsll((long long)tied) - 1);
-  } else {                                                    // equal keys: the lowest index among them
-    mi = k == mk ? i : 0x7fffffff;
-    atss_dpp_min_to_lane63(mi);
-    mi = __builtin_amdgcn_readlane(mi, 63);
-  }
-  k = mk;
-  i = mi;
-}
-
 constexpr unsigned short kAtssNone = 0xffffu;                // P <= 65535: no prior has this index
-constexpr int kAtssKeep = 4;                                  // pairs a lane keeps from one scan (12 registers)
 
 __global__ void __launch_bounds__(1024)
 match_atss_kernel(const float4* __restrict__ priors, const AtssLevels lv, int n_levels, const float4* __restrict__ gt,
@@ -476,57 +413,23 @@ match_atss_kernel(const float4* __restrict__ priors, const AtssLevels lv, int n_
         int last_i = -1;
         int taken = 0;
         while (taken < c) {
-          // scan: the lane's kAtssKeep smallest pairs over the last one taken, ascending; (all ones, INT_MAX) = none
-          unsigned long long lk[kAtssKeep];
-          int li[kAtssKeep];
-#pragma unroll
-          for (int t = 0; t < kAtssKeep; ++t) { lk[t] = ~0ull; li[t] = 0x7fffffff; }
-          int eligible = 0;                                   // how many of the lane's pairs are over the last one taken
-          auto offer = [&](const float4 q, int p) {
-            const unsigned long long k = atss_d2_key(q, cxj, cyj);
-            if (!atss_pair_less(last_k, last_i, k, p)) return;
-            ++eligible;
-            if (!atss_pair_less(k, p, lk[kAtssKeep - 1], li[kAtssKeep - 1])) return;
-            lk[kAtssKeep - 1] = k; li[kAtssKeep - 1] = p;
-#pragma unroll
-            for (int t = kAtssKeep - 1; t > 0; --t) {
-              if (atss_pair_less(lk[t], li[t], lk[t - 1], li[t - 1])) {
-                const unsigned long long sk = lk[t]; lk[t] = lk[t - 1]; lk[t - 1] = sk;
-                const int si = li[t]; li[t] = li[t - 1]; li[t - 1] = si;
-              }
-            }
-          };
+          // scan: the lane's kKeepPairs smallest pairs over the last one taken, then the rounds (wave_select.h)
+          KeepList list;
+          list.reset();
           for (int p = lo + lane; p < hi; p += 128) {         // two loads in flight: the scan waits on L2, not on arithmetic
             const int p1 = p + 64;
             const float4 q0 = priors[p], q1 = priors[p1 < hi ? p1 : p];
-            offer(q0, p);
-            if (p1 < hi) offer(q1, p1);
+            list.offer(atss_d2_key(q0, cxj, cyj), p, last_k, last_i);
+            if (p1 < hi) list.offer(atss_d2_key(q1, cxj, cyj), p1, last_k, last_i);
           }
-          // rounds: the smallest head of the 64 lists is the next pair; its lane moves on.  A lane that has handed out its
-          // whole list and had more pairs than it could keep no longer knows its smallest: scan again from the last one.
-          int pops = 0;
-          while (taken < c) {
-            if (__any(pops == kAtssKeep && eligible > kAtssKeep)) break;
-            unsigned long long best_k = lk[0];
-            int best_i = li[0];
-            atss_wave_min(best_k, best_i);
-            if (li[0] == best_i) {                            // indices are distinct: the one lane that holds it
-#pragma unroll
-              for (int t = 0; t + 1 < kAtssKeep; ++t) { lk[t] = lk[t + 1]; li[t] = li[t + 1]; }
-              lk[kAtssKeep - 1] = ~0ull; li[kAtssKeep - 1] = 0x7fffffff;
-              ++pops;
-            }
-            last_k = best_k;
-            last_i = best_i;
-            ++taken;
-          }
+          keep_list_rounds(list, c, taken, last_k, last_i);
         }
         cut_k = last_k;
         cut_i = last_i;
       }
       for (int base = lo; base < hi; base += 64) {            // the priors at or under the cut, in ascending index
         const int p = base + lane;
-        const bool in = p < hi && !atss_pair_less(cut_k, cut_i, atss_d2_key(priors[p], cxj, cyj), p);
+        const bool in = p < hi && !pair_less(cut_k, cut_i, atss_d2_key(priors[p], cxj, cyj), p);
         const unsigned long long mask = __ballot(in);
         const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
         if (in && slot < m) cj[slot] = (unsigned short)p;

@@ -103,6 +103,49 @@ def atss_matches(priors, level_start, gt_bboxes, num_gt_bboxes, status, match, t
     return match, n_extra, thr
 
 
+TAL_ALPHA_DEFAULT, TAL_BETA_DEFAULT = 1.0, 6                  # TOOD's setting
+
+
+def _tal_arguments(tal_topk, tal_alpha, tal_beta):
+    """None (off), or (topk, alpha_halves, beta) as mbx_match_tal takes them.  Raises ValueError on a bad value."""
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if tal_topk is None:
+        if tal_alpha != TAL_ALPHA_DEFAULT or tal_beta != TAL_BETA_DEFAULT or isinstance(tal_alpha, bool) \
+                or isinstance(tal_beta, bool):
+            raise ValueError("tal_alpha / tal_beta are given without tal_topk")
+        return None
+    if not (isinstance(tal_topk, int) and not isinstance(tal_topk, bool) and 1 <= tal_topk <= 2 ** 31 - 1):
+        raise ValueError("tal_topk must be an int >= 1, got %r" % (tal_topk,))
+    if not (number(tal_alpha) and 0.0 <= tal_alpha <= 4.0 and tal_alpha * 2 == int(tal_alpha * 2)):
+        raise ValueError("tal_alpha must be a multiple of 0.5 in [0, 4], got %r" % (tal_alpha,))
+    if not (number(tal_beta) and 1 <= tal_beta <= 16 and tal_beta == int(tal_beta)):
+        raise ValueError("tal_beta must be an int in [1, 16], got %r" % (tal_beta,))
+    return tal_topk, int(tal_alpha * 2), int(tal_beta)
+
+
+def tal_matches(priors, decoded, conf, gt_bboxes, num_gt_bboxes, status, match, topk, alpha=TAL_ALPHA_DEFAULT,
+                beta=TAL_BETA_DEFAULT, n_extra=None, thr=None):
+    """mbx_match_tal (task-aligned matching, TOOD, Feng et al. 2021): priors [P,4] corners, decoded [B,P,4] and conf [B,P]
+    as mbx_match reads them, gt [B,G,4], n [B], status [B] as mbx_match left it, match int32 [B,P] updated IN PLACE -- per
+    box the topk priors with their centre inside it whose prediction scores the largest t = conf^alpha * IoU^beta are
+    selected, and every free prior some box selected goes to the box its prediction overlaps most.  alpha a multiple of
+    0.5 in [0, 4], beta an int in [1, 16].  n_extra int32 [B] and thr float64 [B,G] (both optional) receive the number
+    added per image and the t of each box's last selected prior.  Returns (match, n_extra, thr)."""
+    B, P = match.shape
+    G = gt_bboxes.shape[1]
+    assert priors.shape == (P, 4) and decoded.shape == (B, P, 4) and conf.shape == (B, P) and gt_bboxes.shape == (B, G, 4)
+    assert thr is None or (thr.is_cuda and thr.dtype == torch.float64 and thr.is_contiguous() and thr.shape == (B, G))
+    halves = alpha * 2
+    if isinstance(alpha, bool) or isinstance(beta, bool) or halves != int(halves) or beta != int(beta):
+        raise ValueError("alpha must be a multiple of 0.5 and beta an int, got %r and %r" % (alpha, beta))
+    _lib.check(_lib.lib().mbx_match_tal(_f32(priors).data_ptr(), _f32(decoded).data_ptr(), _f32(conf).data_ptr(),
+                                        _f32(gt_bboxes).data_ptr(), _i32(num_gt_bboxes).data_ptr(),
+                                        _i32(status).data_ptr(), int(topk), int(halves), int(beta), B, P, G,
+                                        _i32(match).data_ptr(), None if n_extra is None else _i32(n_extra).data_ptr(),
+                                        None if thr is None else thr.data_ptr(), _stream()), "mbx_match_tal")
+    return match, n_extra, thr
+
+
 def compute_assignments(locations, confidences, gt_bboxes, num_gt_bboxes, batch_size, alpha):
     """loss.py:8-53.  Same inputs/outputs as the py_func callback: returns
     [assignment_partitions int32 [B*P], stacked_gt_bboxes float32 [M,4]] (row order),
@@ -226,6 +269,16 @@ class MultiboxLoss:
     two cells of a level at k = 5; the paper's nine locations are 9 * k.  What that does to AP on real data is not measured
     here either.
 
+    tal_topk (an int >= 1, 13 in the paper; None = off) with tal_alpha (a multiple of 0.5 in [0, 4], default 1) and tal_beta
+    (an int in [1, 16], default 6; both only with tal_topk): task-aligned matching (TOOD, Feng et al. 2021) in the place of
+    threshold or ATSS matching -- behind mbx_match every box selects the tal_topk priors with their centre inside it whose
+    PREDICTION scores the largest conf^alpha * IoU^beta, and a free prior some box selected becomes a positive of the box
+    its prediction overlaps most (mbx_match_tal, include/mbx.h); the number added per image is left in ``n_tal``, the metric
+    of each box's last selected prior in ``tal_thr``.  Not together with match_iou_threshold or atss_topk: each decides what
+    a free prior becomes.  The bipartite match stays, so every box keeps one guaranteed prior while the predictions still
+    overlap nothing; TOOD's normalised soft target is not part of it, quality_target supplies an IoU target.  What that
+    does to AP on real data is not measured here either.
+
     focal_gamma (a float in [0, 10]; None = off, the reference's loss): the focal loss on the confidence term -- a
     positive's -log c is weighted by w^gamma and a counted negative's -log w by c^gamma (mbx_loss_fwd_bwd_focal,
     include/mbx.h).  focal_alpha (a float inside (0, 1); None = both sides weigh 1; only with focal_gamma) weighs the
@@ -260,7 +313,12 @@ class MultiboxLoss:
     def __init__(self, bbox_priors, batch_size, max_num_bboxes, location_loss_alpha, device="cuda", neg_per_pos=None,
                  min_neg=0, match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
                  atss_topk=None, prior_levels=None, quality_target=None, quality_gamma=None, quality_neg_weight=None,
-                 ignore_iou_threshold=None, ignore_source="prior"):
+                 ignore_iou_threshold=None, ignore_source="prior", tal_topk=None, tal_alpha=TAL_ALPHA_DEFAULT,
+                 tal_beta=TAL_BETA_DEFAULT):
+        self.tal = _tal_arguments(tal_topk, tal_alpha, tal_beta)
+        if self.tal is not None and (match_iou_threshold is not None or atss_topk is not None):
+            raise ValueError("tal_topk and %s are both given: each decides what a free prior becomes"
+                             % ("match_iou_threshold" if match_iou_threshold is not None else "atss_topk"))
         self.focal = _focal_arguments(focal_gamma, focal_alpha)
         self.loc = _loc_arguments(loc_loss, loc_beta)
         self.quality = _quality_arguments(quality_target, quality_gamma, quality_neg_weight)
@@ -350,6 +408,15 @@ class MultiboxLoss:
             self.atss_thr = torch.zeros((self.B, self.G), dtype=torch.float64, device=device)
         elif prior_levels is not None:
             raise ValueError("prior_levels is given without atss_topk")
+        self.tal_topk, self.n_tal, self.tal_thr = None, None, None
+        if self.tal is not None:
+            verdict = l.mbx_match_tal_supported(self.P, self.G, self.tal[0])
+            if verdict != 0:
+                raise ValueError("tal_topk %d with %d priors and %d boxes an image: mbx_match_tal says %s"
+                                 % (self.tal[0], self.P, self.G, l.mbx_status_string(verdict).decode()))
+            self.tal_topk = self.tal[0]
+            self.n_tal = torch.zeros((self.B,), dtype=torch.int32, device=device)
+            self.tal_thr = torch.zeros((self.B, self.G), dtype=torch.float64, device=device)
 
     def forward_backward(self, raw_locs, logits, gt_bboxes, num_gt_bboxes, grad_scale=1.0, conf_is_logit=True):
         """raw_locs [B,P,4], logits [B,P] f32 -> (loss2 [2] = {location_loss, confidence_loss}, d_locs, d_logits)."""
@@ -376,6 +443,11 @@ class MultiboxLoss:
                                         num_gt_bboxes.data_ptr(), self.status.data_ptr(), self.atss_topk, B, P, G,
                                         self.match.data_ptr(), self.n_atss.data_ptr(), self.atss_thr.data_ptr(), s),
                        "mbx_match_atss")
+        if self.tal is not None:
+            _lib.check(l.mbx_match_tal(self.priors.data_ptr(), self.decoded.data_ptr(), self.conf.data_ptr(),
+                                       gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(), self.status.data_ptr(), *self.tal,
+                                       B, P, G, self.match.data_ptr(), self.n_tal.data_ptr(), self.tal_thr.data_ptr(), s),
+                       "mbx_match_tal")
         if self.ignore is not None:
             boxes = self.decoded if self.ignore[1] else self.priors
             _lib.check(l.mbx_match_ignore(boxes.data_ptr(), self.ignore[1], gt_bboxes.data_ptr(), num_gt_bboxes.data_ptr(),

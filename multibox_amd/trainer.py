@@ -50,7 +50,7 @@ class Trainer:
                  n_segments=None, process_group=None, trainable_scopes=None, neg_per_pos=None, min_neg=0,
                  match_iou_threshold=None, focal_gamma=None, focal_alpha=None, loc_loss=None, loc_beta=None,
                  quality_target=None, quality_gamma=None, quality_neg_weight=None,
-                 ignore_iou_threshold=None, ignore_source="prior",
+                 ignore_iou_threshold=None, ignore_source="prior", tal_topk=None, tal_alpha=1.0, tal_beta=6,
                  clip_gradient_norm=None, optimizer="rmsprop", sgd_momentum=0.9, sgd_nesterov=False, adam_beta1=0.9,
                  adam_beta2=0.999, adam_epsilon=1e-8, adamw_weight_decay=0.01, lr_warmup_steps=0, atss_topk=None,
                  layerwise_trust=False, trust_coeff=None):
@@ -67,13 +67,16 @@ class Trainer:
         # at least the threshold is neither positive nor negative (MultiboxLoss; None = off)
         # atss_topk: ATSS matching behind the bipartite match (MultiboxLoss; None = off).  Its pyramid levels are the
         # network's heads: op.head = (cells, k, off), the offsets mbx_head_gather_all uses, in prediction order
+        # tal_topk / tal_alpha / tal_beta: task-aligned matching behind the bipartite match, by the predictions' score and
+        # overlap (MultiboxLoss; None = off)
         prior_levels = None if atss_topk is None else [op.head[2] for op in net.heads] + [net.P]
         self.loss = MultiboxLoss(bbox_priors, net.B, max_num_bboxes, location_loss_alpha, device=net.dev,
                                  neg_per_pos=neg_per_pos, min_neg=min_neg, match_iou_threshold=match_iou_threshold,
                                  focal_gamma=focal_gamma, focal_alpha=focal_alpha, loc_loss=loc_loss, loc_beta=loc_beta,
                                  atss_topk=atss_topk, prior_levels=prior_levels, quality_target=quality_target,
                                  quality_gamma=quality_gamma, quality_neg_weight=quality_neg_weight,
-                                 ignore_iou_threshold=ignore_iou_threshold, ignore_source=ignore_source)
+                                 ignore_iou_threshold=ignore_iou_threshold, ignore_source=ignore_source,
+                                 tal_topk=tal_topk, tal_alpha=tal_alpha, tal_beta=tal_beta)
         assert self.loss.P == net.P, "priors (%d) do not match the network's predictions (%d)" % (self.loss.P, net.P)
         self.loss.d_locs, self.loss.d_logits = net.d_locs, net.d_logits
         self.lr0, self.dsteps, self.lr_factor, self.staircase = initial_learning_rate, decay_steps_, learning_rate_decay_factor, staircase
@@ -784,6 +787,11 @@ class Trainer:
         """Mean over the batch of the priors ATSS matching added to the last step's bipartite match, or None without it --
         host sync; call it at logging intervals."""
         return None if self.loss.n_atss is None else float(self.loss.n_atss.float().mean())
+
+    def tal_matches_per_image(self):
+        """Mean over the batch of the priors task-aligned matching added to the last step's bipartite match, or None without
+        it -- syncs the host."""
+        return None if self.loss.n_tal is None else float(self.loss.n_tal.float().mean())
 
     def ignored_per_image(self):
         """Mean over the batch of the free priors the last step's ignore band took out of the confidence loss, or None

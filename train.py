@@ -48,7 +48,7 @@ def main():
     args = parse_args()
     import numpy as np
     import torch
-    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, quality_loss, grad_clip, optimizer, atss_matching, layerwise_trust, ignore_band
+    from multibox_amd.config import parse_config_file, with_defaults, negative_mining, match_iou_threshold, focal_loss, loc_loss, quality_loss, grad_clip, optimizer, atss_matching, layerwise_trust, ignore_band, tal_matching
     from multibox_amd import priors as PR, checkpoint as CK
     from multibox_amd.engine import Net
     from multibox_amd.trainer import Trainer, decay_steps
@@ -74,6 +74,7 @@ def main():
         mining = negative_mining(cfg)
         match_iou = match_iou_threshold(cfg)      # [new] LOSS_MATCH_IOU_THRESHOLD: threshold matching, off when absent
         atss_topk = atss_matching(cfg)            # [new] LOSS_MATCH_ATSS_TOPK: ATSS matching, off when absent
+        tal = tal_matching(cfg)                   # [new] LOSS_MATCH_TAL_TOPK (+ _ALPHA, _BETA): task-aligned matching, off when absent
         focal = focal_loss(cfg)                   # [new] LOSS_FOCAL_GAMMA / LOSS_FOCAL_ALPHA: focal loss, off when absent
         loc_term = loc_loss(cfg)                  # [new] LOSS_LOC_TYPE / LOSS_LOC_BETA: the location term, L2 when absent
         quality = quality_loss(cfg)               # [new] LOSS_QUALITY_TARGET (+ _GAMMA, _NEG_WEIGHT): IoU-aware confidence target, off when absent
@@ -106,7 +107,7 @@ def main():
                  match_iou_threshold=match_iou, focal_gamma=focal[0] if focal else None,
                  focal_alpha=focal[1] if focal else None, loc_loss=loc_term[0] if loc_term else None,
                  loc_beta=loc_term[1] if loc_term else None, clip_gradient_norm=clip_norm, atss_topk=atss_topk, **opt, **(trust or {}),
-                 **(quality or {}), **(ignore or {}))
+                 **(quality or {}), **(ignore or {}), **(tal or {}))
     if args.trainable_scopes and rank == 0:       # train.py:166-169
         print("Trainable Variables")
         for name in tr.trainable_names:
@@ -199,6 +200,8 @@ def main():
                 rec["extra_matches_per_image"] = tr.extra_matches_per_image()
             if atss_topk is not None:
                 rec["atss_topk"], rec["atss_matches_per_image"] = atss_topk, tr.atss_matches_per_image()
+            if tal:
+                rec.update(tal, tal_matches_per_image=tr.tal_matches_per_image())
             if focal:
                 rec["focal_gamma"], rec["focal_alpha"] = focal
             rec.update(loc_log_fields(loc_term))

@@ -37,7 +37,12 @@ def parse_args():
                         "(absent or null = off; linear or gaussian) replaces the greedy NMS by Soft-NMS: an overlapping "
                         "candidate's score is lowered (linear: by 1 - IoU above MERGE_IOU_THRESHOLD; gaussian: by "
                         "exp(-IoU^2 / MERGE_SOFT_NMS_SIGMA), default 0.5) instead of the candidate deleted, candidates at or "
-                        "below MERGE_SOFT_NMS_MIN_SCORE (default 0.001) are dropped, and the file carries the decayed scores")
+                        "below MERGE_SOFT_NMS_MIN_SCORE (default 0.001) are dropped, and the file carries the decayed scores; "
+                        "DETECTION.MERGE_WBF (absent or null = off; avg or max) replaces all of that by weighted boxes fusion: "
+                        "candidates that overlap a cluster's running fused box by more than MERGE_WBF_IOU_THRESHOLD (default "
+                        "0.55) join it, the file carries each cluster's score-weighted mean box and the mean (avg) or first "
+                        "(max) score of its members, scaled down when fewer than MERGE_WBF_EXPECTED_VIEWS (default 1) "
+                        "candidates agree; candidates at or below MERGE_WBF_MIN_SCORE (default 0.0) take no part")
     p.add_argument("--keep_partial_batch", action="store_true",
                    help="[new] also process the last incomplete batch (the reference's tf.train.batch drops it)")
     return p.parse_args()
@@ -93,6 +98,31 @@ def main():
             elif "MERGE_IOU_THRESHOLD" in det_keys and rank == 0:
                 print("DETECTION.MERGE_IOU_THRESHOLD is ignored: gaussian Soft-NMS (DETECTION.MERGE_SOFT_NMS) has no IoU threshold")
             merge_soft = (det_keys["MERGE_SOFT_NMS"],) + merge_soft[1:]
+    # DETECTION.MERGE_WBF (absent or null = off, avg, max), MERGE_WBF_IOU_THRESHOLD (0.55), MERGE_WBF_MIN_SCORE (0.0) and
+    # MERGE_WBF_EXPECTED_VIEWS (1): weighted boxes fusion in the per-image merge, read and checked like the keys above.  It
+    # has its own threshold (MERGE_IOU_THRESHOLD is not read) and composes with neither Soft-NMS nor box voting
+    merge_wbf = None
+    if args.merge_per_image:
+        wbf_keys = ("MERGE_WBF_IOU_THRESHOLD", "MERGE_WBF_MIN_SCORE", "MERGE_WBF_EXPECTED_VIEWS")
+        try:
+            merge_wbf = REC.merge_wbf(det_keys.get("MERGE_WBF", None), det_keys.get(wbf_keys[0], 0.55),
+                                      det_keys.get(wbf_keys[1], 0.0), det_keys.get(wbf_keys[2], 1))
+        except ValueError as e:
+            raise SystemExit("DETECTION.MERGE_WBF / %s: %s" % (" / ".join(wbf_keys), e))
+        if merge_wbf is None:
+            given = [k for k in wbf_keys if k in det_keys]
+            if given:
+                raise SystemExit("DETECTION.%s: read with DETECTION.MERGE_WBF (avg or max) only, which is absent or null"
+                                 % " / ".join(given))
+        else:
+            for key, on in (("MERGE_SOFT_NMS", merge_soft is not None), ("MERGE_VOTE_IOU_THRESHOLD", merge_vote_iou is not None)):
+                if on:
+                    raise SystemExit("DETECTION.MERGE_WBF and DETECTION.%s: weighted boxes fusion composes with neither "
+                                     "Soft-NMS nor box voting; give one of the two keys" % key)
+            if "MERGE_IOU_THRESHOLD" in det_keys and rank == 0:
+                print("DETECTION.MERGE_IOU_THRESHOLD is ignored: weighted boxes fusion (DETECTION.MERGE_WBF) has its own, "
+                      "MERGE_WBF_IOU_THRESHOLD")
+            merge_wbf = (det_keys["MERGE_WBF"],) + merge_wbf[1:]
     torch.cuda.set_device(local_rank)
     if world > 1:       # results are gathered as host objects: gloo is enough, no GPU collective on this path
         torch.distributed.init_process_group("gloo")
@@ -209,7 +239,8 @@ def main():
         # DETECTION.MERGE_IOU_THRESHOLD (not a key of the reference): 0.5 when absent, null = no suppression (top-N per image)
         merge_iou = det.get("MERGE_IOU_THRESHOLD", 0.5)
         if rank == 0:
-            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou, vote_iou=merge_vote_iou, soft=merge_soft)
+            merger = D.ImageMerger(max_keep, args.max_detections, merge_iou, vote_iou=merge_vote_iou, soft=merge_soft,
+                                   wbf=merge_wbf)
 
     def merge_feed(hb, hs, hc, ids_, hw_last):
         merger.add(hb, hs, hc, ids_)

@@ -604,6 +604,51 @@ int mbx_merge_detections_soft(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, c
                               int32_t* out_src /*[I,max_det]*/, int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/,
                               int32_t* out_votes /*[I,max_det]; NULL iff vote_iou_threshold == 0*/, mbx_stream_t stream);
 
+/* WEIGHTED BOXES FUSION in the per-image merge (Solovyev, Wang, Gabruseva 2021; optional, off by default in detect.py):
+ * the three entry points above select among an image's candidates; this one clusters them against the running fused box
+ * of each cluster, reports the clusters, and scores a cluster by how many candidates agree on it.  The inputs, the
+ * candidate set (slots [0, clamp(count[r], 0, k_max)) of the image's rows), the flat index row * k_max + slot,
+ * out_status 1 with out_count 0 above MBX_MERGE_MAX_CANDIDATES, I == 0 (MBX_OK, nothing launched) and max_det > 640
+ * (MBX_ERR_UNSUPPORTED) are those of mbx_merge_detections.  R is the number of rows of boxes / scores / count; an image
+ * whose rows are not within [0, R] gets out_status 2 and out_count 0, and nothing of it is read.  Per image:
+ *   1. t_c = (double)score_c.  A candidate is LIVE iff t_c is finite and t_c > min_score.  Everything else (NaN, +-inf, 0,
+ *      negatives, anything at or below min_score) takes no part anywhere.
+ *   2. the live candidates are walked by score descending, ties by ascending flat index (the order of the plain merge).
+ *   3. clusters are numbered in creation order.  For candidate c with box x, area a = (x2 - x1) * (y2 - y1), weight t:
+ *      against every existing cluster k, o_k = IoU(F_k, x) -- the float64 IoU of mbx_nms, term by term, with the fused
+ *      box as the EARLIER box and the stored areas A_k and a (iw = min(F.x2, x.x2) - max(F.x1, x.x1), ih alike;
+ *      inter = iw > 0 && ih > 0 ? iw * ih : 0; uni = A_k + a - inter; o = uni > 0 ? inter / uni : 0).  m = the cluster
+ *      with the largest o_k, bit-equal values to the lowest k.
+ *        o_m > iou_threshold (strict): c JOINS m.  S_m += t; X_mj += t * x_j for j = 0..3 (the product rounded once,
+ *               then the sum; no fused multiply-add); n_m += 1; F_mj = X_mj / S_m; A_m = (F_m2 - F_m0) * (F_m3 - F_m1).
+ *        otherwise c FOUNDS a cluster: S = t, X_j = t * x_j, n = 1, F = x's own bytes, A = a, first = c's flat index.
+ *   4. the cluster's score in float64: q = S / (double)n (MBX_WBF_AVG) or the t of its first member (MBX_WBF_MAX); if
+ *      expected_views > 1, q = (q * (double)min(n, expected_views)) / (double)expected_views.  out_scores = (float)q.
+ *   5. clusters go out by the order image of that float32 score, descending, ties by ascending cluster number, cut to
+ *      max_det: out_boxes = F (a cluster with n == 1 therefore carries its candidate's own bytes), out_src = first,
+ *      out_votes = n, out_count = min(clusters, max_det).  Unused slots 0 / 0 / -1 / 0.
+ * Every operation is one rounded float64 operation in a stated order and the walk is sequential, so all outputs are exact
+ * against a numpy restatement; they depend on the image's own rows only -- not on I, its place in the launch or the
+ * other images -- and the same input gives the same bytes on every call.  iou_threshold = 1 never joins anything: for
+ * inputs whose scores are all live the outputs then equal mbx_merge_detections with iou_threshold = +infinity.
+ * workspace: mbx_merge_wbf_workspace(R, k_max) bytes of device memory, 8-byte aligned, contents irrelevant before and
+ * after the call (host only; 0 for sizes it refuses: R <= 0, k_max <= 0, R * k_max >= 2^31).
+ * MBX_ERR_INVALID_ARG, nothing launched: conf_type not 1 or 2; iou_threshold NaN or outside [0, 1]; min_score NaN,
+ * negative or infinite; expected_views < 1; a null out_votes or workspace; workspace_bytes below what
+ * mbx_merge_wbf_workspace returns (or a size it refuses); everything the plain merge rejects.  One workgroup per image,
+ * one launch; every live candidate is a sequential step with a pass over the image's clusters.  Whether fusion raises AP
+ * on real data is NOT measured here: no trained model or dataset is at hand.                                          */
+#define MBX_WBF_AVG 1
+#define MBX_WBF_MAX 2
+size_t mbx_merge_wbf_workspace(int R, int k_max);
+int mbx_merge_detections_wbf(const double* boxes /*[R,k_max,4] x1,y1,x2,y2*/, const float* scores /*[R,k_max]*/,
+                             const int32_t* count /*[R]*/, const int32_t* image_rows /*[I+1] ascending*/, int R, int I,
+                             int k_max, int max_det, int conf_type, double iou_threshold, double min_score,
+                             int expected_views, double* out_boxes /*[I,max_det,4]*/, float* out_scores /*[I,max_det]*/,
+                             int32_t* out_src /*[I,max_det]*/, int32_t* out_count /*[I]*/, int32_t* out_status /*[I]*/,
+                             int32_t* out_votes /*[I,max_det]*/, void* workspace, size_t workspace_bytes,
+                             mbx_stream_t stream);
+
 /* ------------------------------------------------------ COCO metric: matching (eval.py:212-226)
  * Replaces the matching step of the metric eval.py:212-226 runs: pycocotools' COCOeval.evaluateImg (iouType 'bbox',
  * useCats = 0, no crowd annotations), once per image, area range and IoU threshold; multibox_amd/cocoeval.py:_evaluate_img

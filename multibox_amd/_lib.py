@@ -58,6 +58,8 @@ _SIGS = {
     "mbx_merge_detections": (I, [P, P, P, P, I, I, I, C.c_double, P, P, P, P, P, P]),
     "mbx_merge_detections_voted": (I, [P, P, P, P, I, I, I, C.c_double, C.c_double, P, P, P, P, P, P, P]),
     "mbx_merge_detections_soft": (I, [P, P, P, P, I, I, I, I, C.c_double, C.c_double, C.c_double, C.c_double, P, P, P, P, P, P, P]),
+    "mbx_merge_wbf_workspace": (SZ, [I, I]),
+    "mbx_merge_detections_wbf": (I, [P, P, P, P, I, I, I, I, I, C.c_double, C.c_double, I, P, P, P, P, P, P, P, SZ, P]),
     "mbx_coco_match": (I, [P, P, P, P, I, P, I, P, I, P, P, P, P, P]),
     "mbx_coco_accumulate_workspace": (SZ, [C.c_longlong, I, I, I]),
     "mbx_coco_accumulate": (I, [P, P, I, P, P, P, I, I, P, I, P, I, P, P, P, SZ, P]),

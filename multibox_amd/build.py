@@ -23,6 +23,7 @@ SOURCES = {
     "match_tal.hip": ["-ffp-contract=off"],
     "postproc.hip": ["-ffp-contract=off"],
     "merge.hip": ["-ffp-contract=off"],
+    "merge_wbf.hip": ["-ffp-contract=off"],
     "cocomatch.hip": ["-ffp-contract=off"],
     "cocoaccum.hip": ["-ffp-contract=off"],
     "conv.hip": ["-munsafe-fp-atomics"],

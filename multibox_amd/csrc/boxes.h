@@ -55,4 +55,56 @@ __device__ __forceinline__ void lds_bitonic_sort_desc(unsigned long long* keys, 
   }
 }
 
+// The float a score_order_key came from, but for what the key forgets: -0 comes back as +0, every NaN as one NaN.
+__device__ __forceinline__ float score_from_order_key(unsigned key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+// Step 1 of the per-image merge kernels (merge.hip, merge_wbf.hip), called by all THREADS threads of the workgroup that
+// owns rows [r0, r1): the candidates are the slots [0, clamp(count[r], 0, k_max)) of those rows; key = score_order_key of
+// the score << 32 | ~(offset of the slot from the image's first slot), so that a descending sort gives score descending,
+// ties by ascending flat index.  keys [MBX_MERGE_MAX_CANDIDATES] is sorted in LDS (bitonic, padded with 0 to a power of
+// two).  Returns the number of candidates, the same in every thread; 0 with *too_many set above the limit, and nothing
+// is sorted then.  tile_cnt [THREADS] and wave_tot [THREADS / 64] are LDS scratch.  Ends on a barrier.
+template <int THREADS>
+__device__ __forceinline__ int sorted_candidate_keys(const float* __restrict__ scores, const int32_t* __restrict__ count,
+                                                     int r0, int r1, int k_max, unsigned long long* keys, int* tile_cnt,
+                                                     int* wave_tot, bool* too_many) {
+  const int tid = threadIdx.x;
+  // ---- 1a. number of candidates
+  int mine = 0;
+  for (int r = r0 + tid; r < r1; r += THREADS) mine += min(max(count[r], 0), k_max);
+  mine = wave_sum(mine);
+  if ((tid & 63) == 0) wave_tot[tid >> 6] = mine;
+  __syncthreads();
+  int total = 0;
+  for (int w = 0; w < THREADS / 64; ++w) total += wave_tot[w];
+  *too_many = total > MBX_MERGE_MAX_CANDIDATES;
+  if (*too_many) total = 0;
+  if (total == 0) return 0;
+  // ---- 1b. keys
+  int N = 64;
+  while (N < total) N <<= 1;
+  int off = 0;
+  for (int t0 = r0; t0 < r1; t0 += THREADS) {
+    const int nrows = min(THREADS, r1 - t0);
+    __syncthreads();                                             // the previous tile's counts have been read
+    if (tid < nrows) tile_cnt[tid] = min(max(count[t0 + tid], 0), k_max);
+    __syncthreads();
+    for (int q = 0; q < nrows; ++q) {
+      const int c = tile_cnt[q];
+      const float* sr = scores + (size_t)(t0 + q) * k_max;
+      const unsigned rel0 = (unsigned)(t0 + q - r0) * (unsigned)k_max;
+      for (int s = tid; s < c; s += THREADS) {
+        keys[off + s] = ((unsigned long long)score_order_key(sr[s]) << 32) | (unsigned long long)(~(rel0 + (unsigned)s));
+      }
+      off += c;
+    }
+  }
+  for (int j = total + tid; j < N; j += THREADS) keys[j] = 0ull;        // below every candidate's key (its score image is > 0)
+  __syncthreads();
+  lds_bitonic_sort_desc(keys, N, tid, THREADS);
+  return total;
+}
+
 }  // namespace

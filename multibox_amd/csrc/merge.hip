@@ -57,43 +57,13 @@ merge_kernel(const double* __restrict__ boxes, const float* __restrict__ scores,
   float* os = out_scores + (size_t)img * max_det;
   int32_t* oi = out_src + (size_t)img * max_det;
 
-  // ---- 1a. number of candidates
-  int mine = 0;
-  for (int r = r0 + tid; r < r1; r += kThreads) mine += min(max(count[r], 0), k_max);
-  mine = wave_sum(mine);
-  if (lane == 0) wave_tot[tid >> 6] = mine;
+  // ---- 1. the sorted candidate list (boxes.h)
   if (tid == 0) sh_nk = 0;
-  __syncthreads();
-  int total = 0;
-  for (int w = 0; w < kWaves; ++w) total += wave_tot[w];
-  const bool too_many = total > kMaxCand;
-  if (too_many) total = 0;
+  bool too_many;
+  const int total = sorted_candidate_keys<kThreads>(scores, count, r0, r1, k_max, keys, tile_cnt, wave_tot, &too_many);
 
   int nk = 0;
   if (total > 0) {
-    // ---- 1b. keys
-    int N = 64;
-    while (N < total) N <<= 1;
-    int off = 0;
-    for (int t0 = r0; t0 < r1; t0 += kThreads) {
-      const int nrows = min(kThreads, r1 - t0);
-      __syncthreads();                                           // the previous tile's counts have been read
-      if (tid < nrows) tile_cnt[tid] = min(max(count[t0 + tid], 0), k_max);
-      __syncthreads();
-      for (int q = 0; q < nrows; ++q) {
-        const int c = tile_cnt[q];
-        const float* sr = scores + (size_t)(t0 + q) * k_max;
-        const unsigned rel0 = (unsigned)(t0 + q - r0) * (unsigned)k_max;
-        for (int s = tid; s < c; s += kThreads) {
-          keys[off + s] = ((unsigned long long)score_order_key(sr[s]) << 32) | (unsigned long long)(~(rel0 + (unsigned)s));
-        }
-        off += c;
-      }
-    }
-    for (int j = total + tid; j < N; j += kThreads) keys[j] = 0ull;      // below every candidate's key (its score image is > 0)
-    __syncthreads();
-    lds_bitonic_sort_desc(keys, N, tid, kThreads);
-
     if (!use_iou) {
       // ---- 2'. no suppression: the first max_det of the sorted list
       nk = min(total, max_det);

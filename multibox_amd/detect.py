@@ -119,15 +119,26 @@ class ImageMerger:
     soft None: greedy suppression, as above.  ("linear" | "gaussian", sigma, min_score) (records.merge_soft_nms checks it):
     Soft-NMS (mbx_merge_detections_soft) -- an overlapping candidate's score is lowered instead of the candidate deleted,
     the scores that come out are the decayed ones, in pick order.  Linear takes iou_threshold as its threshold (None is a
-    ValueError), gaussian ignores it; vote_iou is passed through.  The host-side cut above 16 384 candidates comes first."""
+    ValueError), gaussian ignores it; vote_iou is passed through.  The host-side cut above 16 384 candidates comes first.
+    wbf None: one of the forms above.  ("avg" | "max", iou_threshold, min_score, expected_views) (records.merge_wbf checks
+    it): weighted boxes fusion (mbx_merge_detections_wbf) -- the candidates are clustered against the running fused box of
+    each cluster, and the clusters come out: the score-weighted mean box, and a score that falls when fewer than
+    expected_views candidates agree.  It has its own threshold (iou_threshold is not read) and composes with neither
+    voting nor Soft-NMS: vote_iou and soft must be None.  The host-side cut above 16 384 candidates comes first."""
 
-    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256, vote_iou=None, soft=None):
+    def __init__(self, k_max, max_detections, iou_threshold, device="cuda", flush_images=256, vote_iou=None, soft=None,
+                 wbf=None):
         self.K, self.max_det = int(k_max), int(max_detections)
         self.thr = float("inf") if iou_threshold is None else float(iou_threshold)
         self.vote_iou = REC.merge_vote_iou(vote_iou)
         self.soft = None if soft is None else REC.merge_soft_nms(*soft)
         if self.soft is not None and self.soft[0] == REC.SOFT_NMS_METHODS["linear"] and (iou_threshold is None or self.thr != self.thr):
             raise ValueError("linear Soft-NMS needs an IoU threshold (scores decay above it), not %r" % (iou_threshold,))
+        self.wbf = None if wbf is None else REC.merge_wbf(*wbf)
+        if self.wbf is not None and (self.vote_iou is not None or self.soft is not None):
+            raise ValueError("weighted boxes fusion (wbf) composes with neither box voting (vote_iou) nor Soft-NMS (soft): "
+                             "both must be None, not %r and %r" % (vote_iou, soft))
+        self._ws = None                                     # the fusion's workspace: kept between launches, grows when it must
         self.device, self.flush_images = device, max(1, int(flush_images))
         self.stream = torch.cuda.Stream(device=device)      # its uploads and launches do not queue behind the detect loop
         self._rows, self._ids, self._runs = [], [], 0
@@ -185,7 +196,21 @@ class ImageMerger:
             o_count = torch.empty((n_img,), dtype=torch.int32, device=self.device)
             o_status = torch.empty((n_img,), dtype=torch.int32, device=self.device)
             call = "mbx_merge_detections" if self.vote_iou is None else "mbx_merge_detections_voted"
-            if self.soft is not None:
+            if self.wbf is not None:
+                call = "mbx_merge_detections_wbf"
+                conf, thr, min_score, views = self.wbf
+                need = _lib.lib().mbx_merge_wbf_workspace(len(count), self.K)
+                if self._ws is None or self._ws.numel() < need:
+                    self._ws = None                         # (the old one goes before the new one comes)
+                    self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+                o_votes = torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)
+                _lib.check(_lib.lib().mbx_merge_detections_wbf(d_boxes.data_ptr(), d_scores.data_ptr(), d_count.data_ptr(),
+                                                               d_rows.data_ptr(), len(count), n_img, self.K, self.max_det,
+                                                               conf, thr, min_score, views, o_boxes.data_ptr(),
+                                                               o_scores.data_ptr(), o_src.data_ptr(), o_count.data_ptr(),
+                                                               o_status.data_ptr(), o_votes.data_ptr(), self._ws.data_ptr(),
+                                                               self._ws.numel(), self.stream.cuda_stream), call)
+            elif self.soft is not None:
                 call = "mbx_merge_detections_soft"
                 method, sigma, min_score = self.soft
                 o_votes = None if self.vote_iou is None else torch.empty((n_img, self.max_det), dtype=torch.int32, device=self.device)

@@ -77,6 +77,40 @@ def merge_soft_nms(method, sigma=0.5, min_score=0.001):
     return SOFT_NMS_METHODS[method], sg, ms
 
 
+WBF_CONF_TYPES = {"avg": 1, "max": 2}                # MBX_WBF_AVG, MBX_WBF_MAX (include/mbx.h)
+
+
+def merge_wbf(conf, iou_threshold=0.55, min_score=0.0, expected_views=1):
+    """DETECTION.MERGE_WBF, MERGE_WBF_IOU_THRESHOLD, MERGE_WBF_MIN_SCORE and MERGE_WBF_EXPECTED_VIEWS / ImageMerger(wbf=):
+    conf None = no weighted boxes fusion (None is returned), else "avg" or "max" (a cluster's score: the mean of its
+    members' scores, or its first member's) and the validated (conf id, iou_threshold, min_score, expected_views) that
+    mbx_merge_detections_wbf accepts: iou_threshold a number in [0, 1] (a candidate joins the cluster whose fused box it
+    overlaps by more than this), min_score a finite number >= 0 (candidates at or below it take no part), expected_views
+    an integer >= 1 (the number of patches that normally see an object; a cluster of fewer members is scaled down).
+    Anything else, bools included, is a ValueError."""
+    if conf is None:
+        return None
+    if not isinstance(conf, str) or conf not in WBF_CONF_TYPES:
+        raise ValueError("the weighted boxes fusion score type must be 'avg', 'max' or null (no fusion), not %r" % (conf,))
+
+    def number(value):
+        try:
+            return float("nan") if isinstance(value, (bool, str)) else float(value)
+        except (TypeError, ValueError):
+            return float("nan")
+    thr, ms, ev = number(iou_threshold), number(min_score), number(expected_views)
+    if not (0.0 <= thr <= 1.0):
+        raise ValueError("the weighted boxes fusion IoU threshold (a candidate joins the cluster whose fused box it overlaps "
+                         "by more than this) must be a number in [0, 1], not %r" % (iou_threshold,))
+    if not (0.0 <= ms < float("inf")):
+        raise ValueError("the weighted boxes fusion minimum score (candidates at or below it take no part) must be a finite "
+                         "number >= 0, not %r" % (min_score,))
+    if not (1.0 <= ev < 2.0 ** 31 and ev == int(ev)):
+        raise ValueError("the weighted boxes fusion expected views (the number of patches that normally see an object) must "
+                         "be an integer >= 1, not %r" % (expected_views,))
+    return WBF_CONF_TYPES[conf], thr, ms, int(ev)
+
+
 def group_rows(image_ids):
     """Runs of equal consecutive ids in stream order: (ids, image_rows [len(ids) + 1] int32); image i owns the rows
     [image_rows[i], image_rows[i + 1]).  An id that returns later is a new image; the padding rows of a partial batch
